@@ -11,7 +11,13 @@ Multi-GPU (torchrun, one process per GPU, RCCL): the world is split into ``world
 data-parallel replicas of a ``tp``-way tensor-parallel model (default tp = 1: each GPU serves its
 own batch -> weak scaling). ``value`` = total output tokens of all replicas / max-over-ranks time.
 
-Extra keys (outside the timed region, reported alongside the headline):
+A plain run sets up, warms up, times ``--steps`` steps, writes the last step's output if ``--dump-outputs DIR`` is
+given (``DIR/sequences.npy``: the token matrix ``generate`` returned, float32; the prompts and the weights are seeded, so
+two builds can be compared output for output) and prints the one JSON result line.
+
+``--full`` adds the extra keys (outside the timed region, reported alongside the headline):
+  * ``ttft_ms`` / ``decode_ms_per_token`` / ``decode_tokens_per_sec``: one more prefill of the headline batch on the
+    captured engine, and the decode share of a step derived from it;
   * ``latency_points``: decode ms/token at B = 1/8/32/64 (BASELINE.md protocol: prompt 128, cache for
     256 generated tokens, hipGraph replay, prefill excluded);
   * ``ttft``: time to first token of one ``--ttft-len`` (2048) token prompt at B = 1 (prefill of every layer with
@@ -28,7 +34,8 @@ Extra keys (outside the timed region, reported alongside the headline):
     structure included, without the xGMI link's latency.
 
   python bench.py --gpus 1 --steps 3 --warmup 1
-  torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --model llama3-70b --tp 8
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full
+  torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8 --model llama3-70b --tp 8 --full
 """
 from __future__ import annotations
 
@@ -52,11 +59,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--tp", type=int, default=1)
-    # Serving-throughput operating point: 4096 concurrent sequences per replica (KV cache 103 GB of the 288 GB HBM; ~71
-    # ms per decode step). Against 2048 on one box: 43.5k vs 41.5k tok/s -- the o / down / qkv projections fill the chip
-    # without K splits at M = 4096 (profiles/r6_bench_batch_4096_vs_2048.jsonl); the prefill runs in two row chunks of
-    # 2048 x 128 tokens (runtime/engine.py PREFILL_TOKENS). Latency points are reported separately.
-    ap.add_argument("--batch", type=int, default=4096, help="sequences per replica")
+    # Headline operating point: 2048 concurrent sequences per replica, the batch of every recorded headline
+    # (BENCH_r01..r05.json; ~38 ms per decode step, a generate call ~12 s). ``--batch 4096`` is the larger serving point
+    # (~71 ms per decode step, a generate call ~24 s): 43.5k vs 41.5k tok/s on one box -- the o / down / qkv projections
+    # fill the chip without K splits at M = 4096 (profiles/r6_bench_batch_4096_vs_2048.jsonl), and the prefill runs in
+    # two row chunks of 2048 x 128 tokens (runtime/engine.py PREFILL_TOKENS). As the default it made a step so long that
+    # the recorded command (--steps 20 --warmup 5) no longer produced a result line (BENCH_r06.json: rc 124, no value).
+    # Latency points are reported separately.
+    ap.add_argument("--batch", type=int, default=2048, help="sequences per replica")
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--gen-len", type=int, default=256)
     ap.add_argument("--layers", type=int, default=None, help="debug only: override layer count (INVALID for the metric)")
@@ -76,6 +86,11 @@ def main():
     ap.add_argument("--mp1-batch", type=int, default=256)
     ap.add_argument("--no-calibration", action="store_true")
     ap.add_argument("--json-out", default=None)
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure the extra points (TTFT of "
+                    "the headline batch, latency points, long-prompt TTFT, sampling mode, the 70B proxy / MP 1 points, "
+                    "calibration, and the tensor-parallel points when world > 1); off: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write what the last timed step returned "
+                    "(the token matrix of generate) as DIR/sequences.npy (float32)")
     args = ap.parse_args()
 
     import torch
@@ -84,7 +99,6 @@ def main():
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.models import LLaMAForCausalLM
     from jax_llama_amd import ops
-    from jax_llama_amd.ops import autotune
     from jax_llama_amd.parallel import TPComm, init_distributed
     from jax_llama_amd.runtime import engine as eng_mod
     from jax_llama_amd.runtime.benchmark import (calibration, decode_latency, generate_tokens_per_sec,
@@ -127,21 +141,14 @@ def main():
     elapsed = time.perf_counter() - t0
     ctx.barrier()
     torch.cuda.synchronize(dev)
+    if args.dump_outputs and ctx.tp_rank == 0:  # one file per data-parallel replica (its TP ranks hold the same tokens)
+        _dump_outputs(args.dump_outputs, {"sequences": out}, ctx.dp_rank, world // args.tp)
 
-    # time to first token on the already-captured engine (prefill + first sampled token)
-    eng = get_engine(model, args.batch, max_len)
-    torch.cuda.synchronize(dev)
-    tp0 = time.perf_counter()
-    eng.prefill_only(prompts, None, gc)
-    torch.cuda.synchronize(dev)
-    ttft = time.perf_counter() - tp0
-
-    elapsed, ttft = ctx.all_reduce_max([elapsed, ttft])
+    elapsed = ctx.all_reduce_max([elapsed])[0]
     replicas = world // args.tp
     out_tokens = replicas * args.batch * args.gen_len * args.steps
     value = out_tokens / elapsed
     ms_step = 1000.0 * elapsed / args.steps
-    decode_ms_per_token = (ms_step - 1000.0 * ttft) / max(1, args.gen_len - 1)
     res = {
         "metric": "output_tokens_per_sec",
         "value": round(value, 2),
@@ -164,13 +171,31 @@ def main():
             "parallelism": f"dp{replicas}" + (f"xtp{args.tp}" if args.tp > 1 else ""),
             "mp": args.tp,
         },
-        "ttft_ms": round(1000.0 * ttft, 3),
-        "decode_ms_per_token": round(decode_ms_per_token, 4),
-        "decode_tokens_per_sec": round(replicas * args.batch * 1000.0 / decode_ms_per_token, 2),
         "weight_gb_per_gpu": round(model.weight_bytes() / 1e9, 3),
         "hbm_roofline_ms_per_token": round(model.streamed_weight_bytes_per_token() / 6.29e12 * 1e3, 4),
     }
-    del out, eng
+    del out
+    if not args.full:  # a plain run ends here: the headline alone
+        _plan_choices(res)
+        if ctx.rank == 0:
+            _emit(res, args.json_out)
+        if world > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
+
+    # time to first token on the already-captured engine (prefill + first sampled token)
+    eng = get_engine(model, args.batch, max_len)
+    torch.cuda.synchronize(dev)
+    tp0 = time.perf_counter()
+    eng.prefill_only(prompts, None, gc)
+    torch.cuda.synchronize(dev)
+    ttft = ctx.all_reduce_max([time.perf_counter() - tp0])[0]
+    decode_ms_per_token = (ms_step - 1000.0 * ttft) / max(1, args.gen_len - 1)
+    res["ttft_ms"] = round(1000.0 * ttft, 3)
+    res["decode_ms_per_token"] = round(decode_ms_per_token, 4)
+    res["decode_tokens_per_sec"] = round(replicas * args.batch * 1000.0 / decode_ms_per_token, 2)
+    del eng
     eng_mod._ENGINES.clear()  # free the headline batch's KV cache (103 GB at B = 4096) before the extra points
     torch.cuda.empty_cache()
 
@@ -249,9 +274,7 @@ def main():
     if not args.no_calibration:  # last: the GEMM / copy probes of this box, next to the numbers above
         extra("calibration", lambda: res.__setitem__("calibration", calibration(dev)))
         _box_rooflines(res)
-    res["gemm_plan_choice"] = {f"m{k[0]}_n{k[1]}_k{k[2]}_mode{k[3]}{'_rms' if k[4] else ''}": f"ks{v[0]}_tile{v[1]}"
-                               for k, v in autotune.ksplit_table().items()}
-    res["gemv_variant_choice"] = autotune.variant_table()
+    _plan_choices(res)
 
     # ---- tensor-parallel points: the BASELINE model of MP = world over every GPU of the job, under a watchdog
     if world > 1 and args.tp == 1 and args.tp_model and args.tp_batches and not failed["any"]:
@@ -264,6 +287,35 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def _plan_choices(res):
+    """The GEMM plans and decode-kernel variants the run's shapes picked (read from the tuner's tables)."""
+    from jax_llama_amd.ops import autotune
+    res["gemm_plan_choice"] = {f"m{k[0]}_n{k[1]}_k{k[2]}_mode{k[3]}{'_rms' if k[4] else ''}": f"ks{v[0]}_tile{v[1]}"
+                               for k, v in autotune.ksplit_table().items()}
+    res["gemv_variant_choice"] = autotune.variant_table()
+
+
+DUMP_BYTES = 64 << 20  # upper bound of everything --dump-outputs writes, over all replicas
+
+
+def _dump_outputs(path, arrays, rank, world):
+    """``path/<name>.npy`` (float32; token ids are exact in it) of every array the last timed step returned, one file
+    per data-parallel replica (``rank`` of ``world`` replicas); replicas after the first add ``_rank<r>`` to the name.
+    An array beyond its share of ``DUMP_BYTES`` is cut to a fixed, seeded sample of its rows."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    budget = DUMP_BYTES // (world * len(arrays))
+    for name, t in arrays.items():
+        t = t.detach().cpu()
+        rows = max(1, budget // max(1, 4 * t[0].numel()))
+        if t.shape[0] > rows:
+            pick = torch.randperm(t.shape[0], generator=torch.Generator().manual_seed(0))[:rows].sort().values
+            t = t[pick]
+        suffix = "" if rank == 0 else f"_rank{rank}"
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), t.to(torch.float32).numpy())
 
 
 def _box_rooflines(res):

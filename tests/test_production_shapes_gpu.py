@@ -83,7 +83,7 @@ def test_bench_regime_greedy_matches_small_batch(llama3_8b_2l):
 
 @pytest.mark.timeout(600)
 def test_headline_regime_b4096_prompt128(llama3_8b_2l):
-    """The exact benchmarked regime (bench.py: B = 4096, 128-token prompts): the prefill in two row chunks of
+    """The larger serving point of the benchmark (bench.py --batch 4096, 128-token prompts): the prefill in two row chunks of
     M = 262,144 rows (tile-0 GEMMs, flash prefill; runtime/engine.py PREFILL_TOKENS) and the B = 4096 decode plans
     (tuned tiled GEMMs, v4 attention, the fused-argmax lm_head), 32 generated tokens; 8 rows spread over both chunks
     against the same rows run at B = 8, both judged by the fp32 oracle's teacher-forced argmax gap (reference

@@ -2,6 +2,7 @@
 # The driver's headline run (bench.py defaults) with the tuner's picks written to gpurun_out/tune/ (JLA_TUNE_FILE), so
 # the measured plans can be committed as the packaged table (jax_llama_amd/ops/tune_gfx950.json). Output: gpurun_out/full/.
 set -o pipefail
+EXTRA="--full ${EXTRA:-}"  # every extra point, not the headline alone
 mkdir -p gpurun_out/full gpurun_out/tune
 export JLA_TUNE_FILE=${JLA_TUNE_FILE:-$PWD/gpurun_out/tune/tune_gfx950.json}
 timeout -k 10 1100 python3 -u bench.py ${EXTRA:-} --json-out gpurun_out/full/bench.json > gpurun_out/full/bench.log 2>&1

@@ -22,8 +22,9 @@ def main(paths):
                 continue
             r = json.loads(ln)
             if "metric" in r:
-                print(f"{p}: B={r['config']['global_batch']} {r['value']} tok/s, decode {r['decode_ms_per_token']} ms/tok, "
-                      f"ttft {r['ttft_ms']} ms, step {r['ms_per_step']} ms")
+                # decode / ttft: bench.py --full lines only
+                print(f"{p}: B={r['config']['global_batch']} {r['value']} tok/s, decode {r.get('decode_ms_per_token')} "
+                      f"ms/tok, ttft {r.get('ttft_ms')} ms, step {r['ms_per_step']} ms")
             elif "variant" in r:
                 kb[(r["op"], r["m"])][r["variant"]] = r["us"]
             else:

@@ -8,7 +8,7 @@ mkdir -p gpurun_out/tp2
 export JLA_SINGLE_DEVICE=1 JLA_DIST_BACKEND=gloo
 timeout -k 10 900 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
   --master-port 29517 bench.py --gpus 2 --steps 1 --warmup 1 --layers 4 --batch 256 --latency-batches 1 \
-  --no-sampled --ttft-len 0 --no-calibration --tp-batches 1 32 256 ${EXTRA:-} \
+  --no-sampled --ttft-len 0 --no-calibration --tp-batches 1 32 256 --full ${EXTRA:-} \
   --json-out gpurun_out/tp2/bench_tp2.json > gpurun_out/tp2/bench_tp2.log 2>&1
 rc=$?
 tail -5 gpurun_out/tp2/bench_tp2.log
