@@ -397,9 +397,18 @@ static float* rms_ws_ptr(const c10::optional<Tensor>& rws, int64_t m, size_t* fl
 
 void gemm(Tensor x, Tensor w, int64_t n, int64_t k, Tensor out, int64_t mode, bool accumulate,
           c10::optional<Tensor> mirror, int64_t ksplit, c10::optional<Tensor> ws, double rms_eps, int64_t tile,
-          c10::optional<Tensor> pack_out, c10::optional<Tensor> rms_ws) {
+          c10::optional<Tensor> pack_out, c10::optional<Tensor> rms_ws, int64_t n_body) {
   check_gpu(x, "x");
   check_packed(w, n, k);
+  if (tile == 18 || tile == 19) {  // tail-balanced gemm4: n_body pins the body n-tile count (0: the modelled split)
+    const int64_t wb = jla::gemm_tail_width((int)tile);
+    check(ksplit <= 1 && k % 64 == 0, "gemm tiles 18 / 19: no K split, K % 64 == 0");
+    check(n_body >= 0 && n_body * wb < n, "gemm tiles 18 / 19: the body must leave columns for the tail");
+    check(n_body > 0 || jla::gemm_tail_split((int)((x.size(0) + 255) / 256), (int)n, (int)wb, jla::gemm_num_cus()) > 0,
+          "gemm tiles 18 / 19: no tail split beats the uniform grid for this shape (gemm_tail_split)");
+  } else {
+    check(n_body == 0, "gemm n_body: tiles 18 / 19 only");
+  }
   check(x.dim() == 2 && x.size(1) == k && x.scalar_type() == torch::kBFloat16, "x must be bf16 [M, K]");
   check(mode >= 0 && mode <= 2, "gemm mode");
   check(rms_eps < 0 || mode != 1, "gemm: fused RMS is not available in residual mode");
@@ -429,7 +438,7 @@ void gemm(Tensor x, Tensor w, int64_t n, int64_t k, Tensor out, int64_t mode, bo
   rc(jla::gemm(cbf(x), w.data_ptr(), out.data_ptr(), m, n, k, mode, accumulate,
                out.scalar_type() == torch::kFloat32, mir, pqa.pack ? &pqa : nullptr,
                ksplit > 1 ? ptr<float>(*ws) : nullptr, ksplit > 1 ? ws->numel() : 0, ksplit, stream(),
-               (float)rms_eps, (int)tile, rws, rfl),
+               (float)rms_eps, (int)tile, rws, rfl, (int)n_body),
      "gemm");
 }
 
@@ -807,7 +816,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("gemm", &gemm, py::arg("x"), py::arg("w"), py::arg("n"), py::arg("k"), py::arg("out"), py::arg("mode"),
         py::arg("accumulate"), py::arg("mirror") = py::none(), py::arg("ksplit") = 1, py::arg("ws") = py::none(),
         py::arg("rms_eps") = -1.0, py::arg("tile") = 0, py::arg("pack_out") = py::none(),
-        py::arg("rms_ws") = py::none());
+        py::arg("rms_ws") = py::none(), py::arg("n_body") = 0);
+  // (body, tail) n-tile counts of the tail-balanced gemm4 plan (tiles 18 / 19: width 192 / 256); (0, 0): not offered.
+  // cus = 0: the current device's CU count
+  m.def("gemm_tail_split", [](int64_t tiles_m, int64_t n, int64_t width, int64_t cus) {
+    const int nb = jla::gemm_tail_split((int)tiles_m, (int)n, (int)width, cus > 0 ? (int)cus : jla::gemm_num_cus());
+    return std::make_pair((int64_t)nb, nb > 0 ? (n - nb * width + 127) / 128 : (int64_t)0);
+  }, py::arg("tiles_m"), py::arg("n"), py::arg("width"), py::arg("cus") = 0);
   m.def("gemm_qkv_direct_ok", [](int64_t m, int64_t tile, int64_t k) {
     return jla::gemm_qkv_direct_ok((int)m, (int)tile, (int)k) != 0;
   });

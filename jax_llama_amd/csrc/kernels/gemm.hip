@@ -1061,6 +1061,61 @@ __global__ void __launch_bounds__(256, 1)
   }
 }
 
+// Tail-balanced gemm4 (tile configs 18 / 19): the columns [0, nb * 32 NJB) are cut into nb n-tiles of 32 NJB columns
+// (NJB = 6 / 8: 192 / 256), the rest into nt n-tiles of 128 -- so that a grid whose last round would leave CUs idle
+// (Llama-3-8B gate_up at M = 2048: 1200 tiles of 256 x 192 = 4.69 rounds of 256 CUs) becomes whole rounds of wide
+// tiles plus one round of narrow ones (1024 + 256 workgroups). A workgroup is a body or a tail tile by its dispatch
+// order (the tail workgroups are the last launched), each region with its own XCD remap and m-grouped order. Every
+// workgroup is independent, and runs the main loop and epilogue of the uniform grids (same K order per output
+// element: bit for bit the results of tiles 14 / 16 / 17). No K split, no QKV / argmax epilogue, the norm statistic
+// precomputed (RMSM 0 / 2).
+template <int MODE, int RMSM, int NJ>
+JLA_DEV void g4t_tile(const G4Args& g, const G4Epi& ep, u32x4* lds, int m0, int n0, int wu, int lane) {
+  f32x4 acc[NJ][8];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float ss[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (NJ != 8) {
+    g4n_mainloop<NJ, decltype(acc), true>(g, lds, m0, n0, 0, g.K >> 6, wu, lane, acc);
+  } else {
+    g4_mainloop<false, decltype(acc), 0, true>(g, lds, m0, n0, 0, g.K >> 6, wu, lane, acc, ss);
+  }
+  g4_epilogue<MODE, RMSM, decltype(acc), NJ>(acc, ss, lds, wu, lane, m0, n0, 0, ep, QKVArgs{});
+}
+
+// XCD-aware bijective remap of workgroup `orig` of a region of nwg workgroups (as gemm4_kernel's over the grid; a
+// region that starts at a multiple of 8 keeps orig & 7 = the XCD)
+JLA_DEV int g4t_remap(int orig, int nwg) {
+  const int xcd = orig & 7, q8 = nwg >> 3, r8 = nwg & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (orig >> 3);
+}
+
+template <int MODE, int RMSM, int NJB>
+__global__ void __launch_bounds__(256, 1)
+    gemm4t_kernel(const bf16_t* __restrict__ x, const u32x4* __restrict__ W, void* __restrict__ out, int M, int N,
+                  int K, int accumulate, int out_f32, bf16_t* __restrict__ mirror, int tiles_m, int nb, int nt,
+                  float rms_eps, const float* __restrict__ rms_inv, int group_m) {
+  static_assert(NJB == 6 || NJB == 8, "body tiles: 256 x 192 / 256 x 256");
+  static_assert(RMSM != 1 && MODE != MODE_ARGMAX && MODE != MODE_QKV && MODE != MODE_PARTIAL, "see above");
+  __shared__ u32x4 lds[2 * G4_A_U4 + 3 * G4_B_U4];  // two x + three W slots (160 KiB), both widths
+  const int lane = threadIdx.x & 63;
+  const int wu = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int body = tiles_m * nb, orig = blockIdx.x;
+  const G4Epi ep{out, M, N, K, accumulate, out_f32, mirror, 0, rms_eps, nullptr, rms_inv};
+  int tm, tn;
+  if (orig < body) {
+    g4_tile_coords(g4t_remap(orig, body), tiles_m, nb, tm, tn, group_m);
+    const G4Args g{x, W, out, M, N, K, K >> 6, tiles_m, nb};
+    g4t_tile<MODE, RMSM, NJB>(g, ep, lds, tm * G4_BM, tn * (32 * NJB), wu, lane);
+  } else {
+    g4_tile_coords(g4t_remap(orig - body, tiles_m * nt), tiles_m, nt, tm, tn, group_m);
+    const G4Args g{x, W, out, M, N, K, K >> 6, tiles_m, nt};
+    g4t_tile<MODE, RMSM, 4>(g, ep, lds, tm * G4_BM, nb * (32 * NJB) + tn * 128, wu, lane);
+  }
+}
+
 // Sum of the ksplit fp32 slabs at float4 e4 in split order: the loads of up to 8 splits are issued before the first
 // add (the round-4 loop waited on each split in turn: 12 dependent L2/HBM round trips for the 70B shard's qkv at M =
 // 256, 9 us for 1.3 MB of output). Same addition order as before, so bit for bit the same sums.
@@ -1298,12 +1353,44 @@ size_t gemm_workspace_floats(int M, int N, int K) {
 //   1: 256 x 256, 8 waves (two ping-pong rows) of 128 x 64;   2: 128 x 256, 4 waves of 128 x 64;
 //   3: 128 x 128, 8 waves (two ping-pong rows) of 64 x 32 -- 64 KiB of LDS, so two workgroups can share a CU;
 //      for decode shapes with few 256-wide tiles (o / qkv projections) it replaces split-K partial slabs.
+// gemm4 (below): 7 256 x 256; 13 persistent; 14 the weights three K-tiles deep; 16 / 17 256 x 192 / 128 tiles;
+//   18 / 19 tail-balanced (a body of 256 x 192 / 256 x 256 tiles + a tail of 256 x 128 tiles, gemm4t_kernel).
+// gemm5 (gemm5ws.h): 11 / 12.
 static int tile_cfg(int tile, int M) { return tile >= 1 && tile <= 3 ? tile : (M <= 128 ? 2 : 1); }
 static bool use_g4(int tile, int M, int K);
 // gemm4 on narrower tiles, both with the weights three K-tiles deep (W3; the two-slot forms, tiles 10 / 15, were
 // never picked by the tuner at a bench shape and were removed in round 6):
 constexpr int G4N6D_TILE = 16;  // 256 x 192 tiles (g4n_mainloop<6, W3>)
 constexpr int G4ND_TILE = 17;   // 256 x 128 tiles (g4n_mainloop<4, W3>)
+// tail-balanced gemm4 (gemm4t_kernel): a body of 256 x 192 / 256 x 256 tiles, then one region of 256 x 128 tiles
+constexpr int G4T6_TILE = 18;  // body 192 + tail 128
+constexpr int G4T8_TILE = 19;  // body 256 + tail 128
+static bool is_g4t(int tile) { return tile == G4T6_TILE || tile == G4T8_TILE; }
+int gemm_tail_width(int tile) { return tile == G4T6_TILE ? 192 : (tile == G4T8_TILE ? 256 : 0); }
+
+// The body n-tile count of the tail-balanced plan for tiles_m m-tiles x N columns, body tiles `width` (192 / 256)
+// columns wide, on `cus` CUs; the tail is the remaining columns in 128-wide tiles. Minimises the modelled time
+// rounds x tile width, ceil(tm * n_body / cus) * width + ceil(tm * n_tail / cus) * 128 * (1 + 1/16): the narrow tile
+// moves 1.5x / 2x the operand bytes per MFMA of the 192 / 256 one, which the 1/16 stands for. Ties go to regions that
+// are multiples of 8 workgroups (the XCD count), then to the wider body. 0: no split beats the uniform `width` grid
+// (N already fills whole rounds, or the tail would cost a round of its own for nothing).
+int gemm_tail_split(int tiles_m, int N, int width, int cus) {
+  if (tiles_m <= 0 || N <= 0 || cus <= 0 || (width != 192 && width != 256)) return 0;
+  auto rounds = [&](long long wgs) { return (wgs + cus - 1) / cus; };
+  auto tail_tiles = [&](int nb) { return (N - nb * width + 127) / 128; };
+  auto aligned = [&](int nb) { return (tiles_m * nb) % 8 == 0 && (tiles_m * tail_tiles(nb)) % 8 == 0; };
+  long long best = rounds((long long)tiles_m * ((N + width - 1) / width)) * width * 16;  // the uniform grid
+  int best_nb = 0;
+  for (int nb = (N - 1) / width; nb >= 1; --nb) {
+    const long long cost =
+        rounds((long long)tiles_m * nb) * width * 16 + rounds((long long)tiles_m * tail_tiles(nb)) * 128 * 17;
+    if (cost < best || (best_nb != 0 && cost == best && aligned(nb) && !aligned(best_nb))) {
+      best = cost;
+      best_nb = nb;
+    }
+  }
+  return best_nb;
+}
 int gemm_qkv_direct_ok(int M, int tile, int K) {
   return ((tile == 0 || tile == 1) && tile_cfg(tile, M) == 1) || use_g4(tile, M, K) ||
          (tile == G4N6D_TILE && (K & 63) == 0);
@@ -1406,10 +1493,38 @@ static void launch_g4(const bf16_t* x, const u32x4* w, void* out, int M, int N, 
 #undef JLA_G4
 }
 
+// tile configs 18 / 19: n_body body n-tiles of 32 NJB columns, the rest in 128-wide tiles (gemm() has checked the
+// plan: no K split, 0 < n_body * 32 NJB < N, the norm statistic's scratch)
+template <int MODE, int NJB>
+static void launch_g4t(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate, int out_f32,
+                       bf16_t* mirror, float rms_eps, hipStream_t s, float* rms_ws, int n_body) {
+  const int tm = (M + G4_BM - 1) / G4_BM, nt = (N - n_body * 32 * NJB + 127) / 128;
+  const bool rms = MODE != MODE_RESIDUAL && rms_eps >= 0.f;
+  const int grid = tm * (n_body + nt);
+  const int gm = g4_group_m(tm, n_body, K);
+  if (rms) {
+    if (rms_ws == nullptr || rms_rowinv(x, rms_ws, M, K, rms_eps, s) != 0) return;
+    gemm4t_kernel<MODE, 2, NJB><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, n_body, nt,
+                                                     rms_eps, rms_ws, gm);
+  } else {
+    gemm4t_kernel<MODE, 0, NJB><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, n_body, nt,
+                                                     rms_eps, nullptr, gm);
+  }
+}
+
 template <int MODE>
 static void launch_g2(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate, int out_f32,
                       bf16_t* mirror, int kc, int ksplit, float rms_eps, float* ssq, int tile, hipStream_t s,
-                      const QKVArgs& qa = QKVArgs{}, float* rms_ws = nullptr) {
+                      const QKVArgs& qa = QKVArgs{}, float* rms_ws = nullptr, int n_body = 0) {
+  if constexpr (MODE == MODE_STORE || MODE == MODE_RESIDUAL || MODE == MODE_SWIGLU) {
+    if (is_g4t(tile)) {
+      if (tile == G4T6_TILE)
+        launch_g4t<MODE, 6>(x, w, out, M, N, K, accumulate, out_f32, mirror, rms_eps, s, rms_ws, n_body);
+      else
+        launch_g4t<MODE, 8>(x, w, out, M, N, K, accumulate, out_f32, mirror, rms_eps, s, rms_ws, n_body);
+      return;
+    }
+  }
   if constexpr (MODE != MODE_QKV && MODE != MODE_ARGMAX) {
     if (tile == G4ND_TILE && (K & 63) == 0) {
       launch_g4<MODE, 4>(x, w, out, M, N, K, accumulate, out_f32, mirror, ksplit, rms_eps, ssq, s, qa, rms_ws, false,
@@ -1476,9 +1591,9 @@ static void launch_g2(const bf16_t* x, const u32x4* w, void* out, int M, int N, 
 template <int MODE>
 static void launch_tiled(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate,
                          int out_f32, bf16_t* mirror, int kc, int ksplit, float rms_eps, float* ssq, int tile,
-                         hipStream_t s, float* rms_ws = nullptr) {
+                         hipStream_t s, float* rms_ws = nullptr, int n_body = 0) {
   launch_g2<MODE>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, ksplit, rms_eps, ssq, tile, s, QKVArgs{},
-                  rms_ws);
+                  rms_ws, n_body);
 }
 
 static int g_num_cus = 0;
@@ -1492,6 +1607,7 @@ static int num_cus() {
   }
   return g_num_cus;
 }
+int gemm_num_cus() { return num_cus(); }
 
 // the split-K reduce + epilogue launch over [ksplit][M][N] partial slabs (+ [ksplit][M] sums of squares, fused norm)
 static int launch_reduce(const float* ws, int ksplit, void* out, int M, int N, int K, int mode, int accumulate,
@@ -1570,7 +1686,7 @@ static int launch_g5(const bf16_t* x, const u32x4* w, void* out, int M, int N, i
 
 int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mode, int accumulate, int out_f32,
          bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit, hipStream_t s,
-         float rms_eps, int tile, float* rms_ws, size_t rms_ws_floats) {
+         float rms_eps, int tile, float* rms_ws, size_t rms_ws_floats, int n_body) {
   if (tile == G5_TILE || tile == G5_TILE + 1) {
     if (mode == MODE_ARGMAX || (rms_eps >= 0.f && (mode == MODE_RESIDUAL || mode == MODE_TPRESID))) return -1;
     return launch_g5(x, static_cast<const u32x4*>(W), out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ws,
@@ -1599,6 +1715,16 @@ int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mod
   if ((tile == G4ND_TILE || tile == G4N6D_TILE) && rms &&
       (ksplit > 1 || rms_ws == nullptr))
     return -6;
+  // the tail-balanced plans: store / residual / SwiGLU without a K split, the norm as the precomputed statistic;
+  // n_body > 0 pins the body n-tile count (tests), else the modelled best split -- none (-7) where the uniform grid
+  // already fills whole rounds
+  if (is_g4t(tile)) {
+    if ((K & 63) || ksplit > 1 || (mode != MODE_STORE && mode != MODE_RESIDUAL && mode != MODE_SWIGLU)) return -1;
+    if (rms && rms_ws == nullptr) return -6;
+    const int wb = gemm_tail_width(tile);
+    if (n_body <= 0) n_body = gemm_tail_split((M + G4_BM - 1) / G4_BM, N, wb, num_cus());
+    if (n_body <= 0 || (long long)n_body * wb >= N) return -7;
+  }
   const u32x4* w = static_cast<const u32x4*>(W);
   if (ksplit == 1) {
     switch (mode) {
@@ -1607,14 +1733,15 @@ int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mod
         break;
       case MODE_STORE:
         launch_tiled<MODE_STORE>(x, w, out, M, N, K, accumulate, out_f32, nullptr, kc, 1, rms_eps, nullptr, tile, s,
-                                 rms_ws);
+                                 rms_ws, n_body);
         break;
       case MODE_RESIDUAL:
-        launch_tiled<MODE_RESIDUAL>(x, w, out, M, N, K, accumulate, 1, mirror, kc, 1, -1.f, nullptr, tile, s);
+        launch_tiled<MODE_RESIDUAL>(x, w, out, M, N, K, accumulate, 1, mirror, kc, 1, -1.f, nullptr, tile, s, nullptr,
+                                    n_body);
         break;
       case MODE_SWIGLU:
         launch_tiled<MODE_SWIGLU>(x, w, out, M, N, K, accumulate, 0, nullptr, kc, 1, rms_eps, nullptr, tile, s,
-                                  rms_ws);
+                                  rms_ws, n_body);
         break;
       default: return -1;
     }

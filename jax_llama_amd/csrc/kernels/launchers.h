@@ -89,7 +89,13 @@ size_t gemm_workspace_floats(int M, int N, int K);
 int gemm_tp_groups(int M, int N);
 int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mode, int accumulate, int out_f32,
          bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit, hipStream_t s,
-         float rms_eps = -1.f, int tile = 0, float* rms_ws = nullptr, size_t rms_ws_floats = 0);
+         float rms_eps = -1.f, int tile = 0, float* rms_ws = nullptr, size_t rms_ws_floats = 0, int n_body = 0);
+// tile configs 18 / 19 (tail-balanced gemm4: body tiles of gemm_tail_width(tile) columns, then 128-wide tail tiles):
+// n_body > 0 pins the body n-tile count, 0 takes gemm_tail_split(m-tiles, N, width, CUs) -- 0 from that: no split beats
+// the uniform grid of that width, and gemm() returns -7
+int gemm_tail_width(int tile);
+int gemm_tail_split(int tiles_m, int N, int width, int cus);
+int gemm_num_cus();  // CUs of the current device
 // rms_ws (>= M floats): with the fused norm, a gemm4 plan without a K split computes the row statistic ahead of
 // the GEMM into it (rms_rowinv) instead of inside its main loop; null: in-loop statistic
 // greedy lm_head: GEMM + first-max argmax epilogue (ws >= gemm_argmax_workspace_floats(M, N) floats)

@@ -82,7 +82,7 @@ def tune_file() -> str:
     return os.path.join(base, "jax_llama_amd", f"tune_{ARCH}.json")
 
 
-TUNE_VERSION = 12  # bumped when a candidate set changes (2: split-K GEMV 16-19; 3: 4-tile split-K 26; 4: gemm4 tile 7; 5: gemm4 stream-K; 6: never-picked GEMV variants removed; 7: gemm4 256 x 128 tiles; 8: gemm5 tiles 11 / 12; 9: gemm4 rasterised in groups of 4 m-tiles; 10: stream-K / hybrid plans replaced by the exchange split; 11: gemm4 with the weights three K-tiles deep, 256 x 192 tiles; 12: the never-picked tiles 8 / 10 / 15 removed), so older persisted picks are re-measured
+TUNE_VERSION = 13  # bumped when a candidate set changes (2: split-K GEMV 16-19; 3: 4-tile split-K 26; 4: gemm4 tile 7; 5: gemm4 stream-K; 6: never-picked GEMV variants removed; 7: gemm4 256 x 128 tiles; 8: gemm5 tiles 11 / 12; 9: gemm4 rasterised in groups of 4 m-tiles; 10: stream-K / hybrid plans replaced by the exchange split; 11: gemm4 with the weights three K-tiles deep, 256 x 192 tiles; 12: the never-picked tiles 8 / 10 / 15 removed; 13: tail-balanced gemm4 tiles 18 / 19), so older persisted picks are re-measured
 
 
 def _key_str(kind: str, key: Tuple) -> str:
@@ -300,11 +300,14 @@ _KS_CACHE: Dict[Tuple, Tuple[int, int]] = {}
 KS_CANDIDATES = (1, 2, 3, 4, 6, 8, 12, 16)
 # tile configs: 1 / 2 / 3 gemm2 256x256, 128x256, 128x128 (csrc/kernels/gemm.hip tile_cfg); 7 gemm4; 14 gemm4 with the
 # weights three K-tiles deep (160 KiB of LDS); 17 / 16 gemm4 on 256 x 128 / 192 tiles with the deep weights (no K split
-# under the fused norm, its statistic is precomputed); 11 / 12: gemm5, the weight-streaming split-K kernel (gemm5ws.h;
-# 256 / 128 columns per workgroup, M <= 256 per tile). What the bench shapes pick (BENCH_r05 gemm_plan_choice):
-#   Llama-3-8B M = 1024 / 2048: qkv 16 / 17, o 17, gate_up 7 / 14 / 16, down 14 / 17 (split 2), lm_head 14;
+# under the fused norm, its statistic is precomputed); 18 / 19 tail-balanced gemm4: a body of 256 x 192 / 256 tiles in
+# whole rounds of the CUs, then the remaining columns as 256 x 128 tiles (gemm.hip gemm4t_kernel; same guards as 16 / 17,
+# never split, offered only where gemm_tail_split finds a split that beats the uniform grid); 11 / 12: gemm5, the
+# weight-streaming split-K kernel (gemm5ws.h; 256 / 128 columns per workgroup, M <= 256 per tile). What the bench shapes
+# pick (BENCH_r05 gemm_plan_choice; gate_up at M = 2048: profiles/gemm4t_kernel_ab.jsonl):
+#   Llama-3-8B M = 1024 / 2048: qkv 16 / 17, o 17, gate_up 7 / 14 / 19, down 14 / 17 (split 2), lm_head 14;
 #   Llama-3-70B M = 256 (MP 1 and the MP 8 shard): 1 / 3 (split 4 / 12), 11 / 12 (gemm5 splits), 14, 17.
-TILE_CANDIDATES = (1, 2, 3, 7, 11, 12, 14, 16, 17)
+TILE_CANDIDATES = (1, 2, 3, 7, 11, 12, 14, 16, 17, 18, 19)
 if os.environ.get("JLA_TUNE_TILES"):  # A/B tooling: restrict the tile candidates, e.g. JLA_TUNE_TILES=1,2,3,7,11,12
     TILE_CANDIDATES = tuple(int(v) for v in os.environ["JLA_TUNE_TILES"].split(","))
 # decode-sized M measured per shape (above: the C++ heuristic; prefill-sized M have enough 256 x 256 tiles)
@@ -345,6 +348,7 @@ def choose_gemm_ksplit(e, m: int, n: int, k: int, device) -> int:
 
 
 G4N_TILES = (16, 17)  # gemm4 on 256 x 192 / 128 tiles (csrc/kernels/gemm4w.h g4n_mainloop, deep weights)
+G4T_TILES = {18: 192, 19: 256}  # tail-balanced gemm4: body tile width (the tail tiles are 128 wide; gemm.hip gemm4t_kernel)
 G5_TILES = (11, 12)  # gemm5 weight-streaming split-K (csrc/kernels/gemm5ws.h)
 TUNE_ROUNDS = 3
 
@@ -363,6 +367,8 @@ def _measure_plan(e, m, n, k, device, heur, mode=0, rms=False) -> Tuple[int, int
     ks_c = sorted({c for c in KS_CANDIDATES if kt // c >= 4 and fits(c)} | ({heur} if fits(heur) else set()) | {1})
     cands = [(c, tm) for tm in TILE_CANDIDATES for c in ks_c
              if (tm not in G4N_TILES or (k % 64 == 0 and not (c > 1 and rms and mode != 1)))
+             and (tm not in G4T_TILES or (k % 64 == 0 and c == 1
+                                          and e.gemm_tail_split((m + 255) // 256, n, G4T_TILES[tm])[0] > 0))
              and (tm not in G5_TILES or (k % 64 == 0 and m <= 512))]
     if k % 64 == 0 and m <= 512:  # gemm5 also at the deeper splits its 64-deep stages allow (narrow shards, long K)
         cands += [(c, tm) for tm in G5_TILES for c in (24, 32, 48) if (k // 64) // c >= 2 and c not in ks_c and fits(c)]

@@ -104,6 +104,8 @@ def main():
                     kk = ks or e.gemm_ksplit(m, n, k)
                     if tile in (16, 17) and kk > 1 and eps > 0:
                         continue  # (gemm4 256 x 128 / 192: no K split under the fused norm)
+                    if tile in (18, 19) and (kk > 1 or e.gemm_tail_split((m + 255) // 256, n, 192 if tile == 18 else 256)[0] == 0):
+                        continue  # (tail-balanced gemm4: no K split; only where a split beats the uniform grid)
                     if kk > 1 and (k // 32) // kk < 4 and tile not in (11, 12):
                         continue
                     if tile in (11, 12) and (k % 64 or (k // 64) // kk < 1):
