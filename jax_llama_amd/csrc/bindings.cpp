@@ -8,11 +8,6 @@
 
 #include "kernels/launchers.h"
 
-#define MODE_RESIDUAL_ID 1
-#define MODE_QKV_ID 3
-#define MODE_TPRESID_ID 9
-#define MODE_ARGMAX_ID 8  // common.h MODE_ARGMAX
-
 namespace {
 
 using torch::Tensor;
@@ -29,6 +24,18 @@ void check_gpu(const Tensor& t, const char* name) {
 void rc(int r, const char* what) {
   TORCH_CHECK(r == 0, "jax_llama_amd._C: ", what, " failed (code ", r, ")");
 }
+
+// jla::gemm's return codes (kernels/gemm_plan.h: the one place that decides them) in words
+void gemm_rc(int r, const char* what) {
+  const char* why = r == -1   ? "no legal plan for this shape / tile id / epilogue / fused norm / K split"
+                    : r == -3 ? "the slab workspace is missing or too small"
+                    : r == -5 ? "fused RMS is not available in residual mode"
+                    : r == -6 ? "this tile takes the fused norm only from rms_ws and without a K split"
+                    : r == -7 ? "tiles 18 / 19: no tail split beats the uniform grid for this shape (gemm_tail_split)"
+                              : "HIP error";
+  TORCH_CHECK(r == 0, "jax_llama_amd._C: ", what, " failed (code ", r, ": ", why, "; see gemm_plan.h)");
+}
+bool is_g5(int64_t tile) { return tile == jla::G5_TILE || tile == jla::G5N_TILE; }  // slabs for any split
 
 template <typename T>
 T* ptr(const Tensor& t) {
@@ -235,7 +242,7 @@ void linear_skinny_argmax(Tensor x, Tensor w, int64_t n, int64_t k, double rms_e
         "argmax outputs");
   jla::QKVArgs qa{};
   rc(jla::linear_skinny(x.data_ptr(), x.scalar_type() == torch::kFloat32, w.data_ptr(), part.data_ptr(), m, n, k,
-                        MODE_ARGMAX_ID, (float)rms_eps, 0, 1, &qa, variant, stream()),
+                        MODE_ARGMAX, (float)rms_eps, 0, 1, &qa, variant, stream()),
      "linear_skinny_argmax");
   rc(jla::argmax_partials(ptr<float>(part), n / 16, m, ptr<int32_t>(idx), ptr<float>(val), stream()), "argmax_partials");
 }
@@ -292,7 +299,7 @@ void linear_qkv(Tensor x, Tensor w, int64_t n, int64_t k, double rms_eps, Tensor
   const int64_t m = x.size(0);
   check(m <= SKINNY_MAX_M, "linear_qkv: M too large");
   jla::QKVArgs qa = qkv_args(m, n, table, positions, kc, vc, slot, seq_len, h, hkv, dh, q);
-  run_skinny(x, w, n, k, nullptr, MODE_QKV_ID, rms_eps, false, false, &qa, variant, ws, tickets,
+  run_skinny(x, w, n, k, nullptr, MODE_QKV, rms_eps, false, false, &qa, variant, ws, tickets,
              packed_ptr(x_packed, m, k, "x_packed"));
 }
 
@@ -350,13 +357,13 @@ void linear_qkv_attn(Tensor x, Tensor w, int64_t n, int64_t k, double rms_eps, T
     oh = ptr<float>(*o_h);
     qo.res_bf16 = bf(*o_hb);
     qo.pack = packed_ptr(o_hb_pack, m, o_n, "o_hb_pack");
-    o_mode = MODE_RESIDUAL_ID;
+    o_mode = MODE_RESIDUAL;
     if (tp_state) {
       void* st = reinterpret_cast<void*>(tp_state);
       check(og <= jla::CAR_WG_COUNTERS && og * jla::TPRES_REGION <= jla::car_max_bytes(st),
             "linear_qkv_attn: too many o workgroups for the TP buffer");
       qo.tp = jla::car_device(st);
-      o_mode = MODE_TPRESID_ID;
+      o_mode = MODE_TPRESID;
     }
   }
   rc(jla::linear_qkv_attn(xp ? xp : cbf(x), w.data_ptr(), m, n, k, (float)rms_eps, qa, xp != nullptr, bf(out),
@@ -367,20 +374,16 @@ void linear_qkv_attn(Tensor x, Tensor w, int64_t n, int64_t k, double rms_eps, T
      "linear_qkv_attn");
 }
 
-void check_gemm_ws(const c10::optional<Tensor>& ws, int64_t ksplit, int64_t m, int64_t n, bool rms = false) {
-  if (ksplit <= 1) return;
-  check(ws.has_value(), "gemm: split-K needs a workspace");
+// The slab workspace of a K split -- [ks][M][N] (+ [ks][M] norm partials); gemm5: for any split, ks its effective
+// split over 64-deep stages. False: this call needs none.
+bool check_gemm_ws(const c10::optional<Tensor>& ws, int64_t k, int64_t ksplit, int64_t m, int64_t n, bool rms,
+                   int64_t tile) {
+  if (!is_g5(tile) && ksplit <= 1) return false;
+  check(ws.has_value(), "gemm: a K split (gemm5: any plan) needs the slab workspace");
   check_gpu(*ws, "gemm ws");
-  check(ws->scalar_type() == torch::kFloat32 && ws->numel() >= ksplit * m * (n + (rms ? 1 : 0)),
-        "gemm ws too small");
-}
-
-// gemm5 (tiles 11 / 12) slab workspace: [ks][M][N] (+ [ks][M] norm partials) for its effective split over 64-deep stages
-void check_g5_ws(const c10::optional<Tensor>& ws, int64_t k, int64_t ksplit, int64_t m, int64_t n, bool rms) {
-  check(ws.has_value(), "gemm tile 11 / 12: the slab workspace is required (any split)");
-  check_gpu(*ws, "gemm ws");
-  const int64_t eks = jla::gemm5_ksplit((int)k, (int)ksplit);
-  check(ws->scalar_type() == torch::kFloat32 && ws->numel() >= eks * m * (n + (rms ? 1 : 0)), "gemm ws too small");
+  const int64_t ks = is_g5(tile) ? jla::gemm5_ksplit((int)k, (int)ksplit) : ksplit;
+  check(ws->scalar_type() == torch::kFloat32 && ws->numel() >= ks * m * (n + (rms ? 1 : 0)), "gemm ws too small");
+  return true;
 }
 
 // Tiled MFMA GEMM; ksplit > 1 -> split-K partials in ws + fixed-order reduce/epilogue kernel.
@@ -400,18 +403,9 @@ void gemm(Tensor x, Tensor w, int64_t n, int64_t k, Tensor out, int64_t mode, bo
           c10::optional<Tensor> pack_out, c10::optional<Tensor> rms_ws, int64_t n_body) {
   check_gpu(x, "x");
   check_packed(w, n, k);
-  if (tile == 18 || tile == 19) {  // tail-balanced gemm4: n_body pins the body n-tile count (0: the modelled split)
-    const int64_t wb = jla::gemm_tail_width((int)tile);
-    check(ksplit <= 1 && k % 64 == 0, "gemm tiles 18 / 19: no K split, K % 64 == 0");
-    check(n_body >= 0 && n_body * wb < n, "gemm tiles 18 / 19: the body must leave columns for the tail");
-    check(n_body > 0 || jla::gemm_tail_split((int)((x.size(0) + 255) / 256), (int)n, (int)wb, jla::gemm_num_cus()) > 0,
-          "gemm tiles 18 / 19: no tail split beats the uniform grid for this shape (gemm_tail_split)");
-  } else {
-    check(n_body == 0, "gemm n_body: tiles 18 / 19 only");
-  }
+  check(n_body >= 0 && (n_body == 0 || jla::gemm_tail_width((int)tile) > 0), "gemm n_body: tail-balanced tiles only");
   check(x.dim() == 2 && x.size(1) == k && x.scalar_type() == torch::kBFloat16, "x must be bf16 [M, K]");
   check(mode >= 0 && mode <= 2, "gemm mode");
-  check(rms_eps < 0 || mode != 1, "gemm: fused RMS is not available in residual mode");
   const int64_t m = x.size(0);
   check_linear_out(out, m, n, mode);
   jla::bf16_t* mir = mode == 1 ? mirror_ptr(mirror, out.numel()) : nullptr;
@@ -421,25 +415,17 @@ void gemm(Tensor x, Tensor w, int64_t n, int64_t k, Tensor out, int64_t mode, bo
   if (pack_out.has_value()) {
     check(m <= SKINNY_MAX_M && (mode == 1 || mode == 2) && (mode != 1 || mir), "gemm pack_out: decode M, residual "
           "(with its mirror) or SwiGLU");
-    check(ksplit > 1 || tile == 11 || tile == 12, "gemm pack_out: the split-K reduce-kernel path only");
+    check(ksplit > 1 || is_g5(tile), "gemm pack_out: the split-K reduce-kernel path only");
     pqa.pack = packed_ptr(pack_out, m, mode == 2 ? n / 2 : n, "pack_out");
   }
-  if (tile == 11 || tile == 12) {  // gemm5 (weight-streaming) partial slabs + the reduce kernel's epilogue, any split
-    check_g5_ws(ws, k, ksplit, m, n, rms_eps >= 0);
-    rc(jla::gemm(cbf(x), w.data_ptr(), out.data_ptr(), m, n, k, mode, accumulate,
-                 out.scalar_type() == torch::kFloat32, mir, pqa.pack ? &pqa : nullptr, ptr<float>(*ws), ws->numel(),
-                 ksplit, stream(), (float)rms_eps, (int)tile, nullptr, 0),
-       "gemm");
-    return;
-  }
-  check_gemm_ws(ws, ksplit, m, n, rms_eps >= 0);
+  const bool slabs = check_gemm_ws(ws, k, ksplit, m, n, rms_eps >= 0, tile);
   size_t rfl = 0;
   float* rws = rms_ws_ptr(rms_ws, m, &rfl);
-  rc(jla::gemm(cbf(x), w.data_ptr(), out.data_ptr(), m, n, k, mode, accumulate,
-               out.scalar_type() == torch::kFloat32, mir, pqa.pack ? &pqa : nullptr,
-               ksplit > 1 ? ptr<float>(*ws) : nullptr, ksplit > 1 ? ws->numel() : 0, ksplit, stream(),
-               (float)rms_eps, (int)tile, rws, rfl, (int)n_body),
-     "gemm");
+  gemm_rc(jla::gemm(cbf(x), w.data_ptr(), out.data_ptr(), m, n, k, mode, accumulate,
+                    out.scalar_type() == torch::kFloat32, mir, pqa.pack ? &pqa : nullptr,
+                    slabs ? ptr<float>(*ws) : nullptr, slabs ? ws->numel() : 0, ksplit, stream(), (float)rms_eps,
+                    (int)tile, rws, rfl, (int)n_body),
+          "gemm");
 }
 
 // Tiled split-K qkv projection with the RoPE + KV-cache write in the reduce epilogue (x: bf16; rms_eps >= 0
@@ -452,28 +438,14 @@ void gemm_qkv(Tensor x, Tensor w, int64_t n, int64_t k, Tensor table, Tensor pos
   check(x.dim() == 2 && x.size(1) == k && x.scalar_type() == torch::kBFloat16, "x must be bf16 [M, K]");
   const int64_t m = x.size(0);
   jla::QKVArgs qa = qkv_args(m, n, table, positions, kc, vc, slot, seq_len, h, hkv, dh, q);
-  if (tile == 11 || tile == 12) {  // gemm5 partial slabs, RoPE / KV write in the reduce kernel
-    check_g5_ws(ws, k, ksplit, m, n, rms_eps >= 0);
-    rc(jla::gemm(cbf(x), w.data_ptr(), nullptr, m, n, k, MODE_QKV_ID, 0, 0, nullptr, &qa, ptr<float>(*ws), ws->numel(),
-                 ksplit, stream(), (float)rms_eps, (int)tile, nullptr, 0),
-       "gemm_qkv");
-    return;
-  }
-  if (ksplit <= 1) {  // no K split: the GEMM's own RoPE / KV-write epilogue (default FA pipeline, fused norm)
-    check(rms_eps >= 0 && jla::gemm_qkv_direct_ok((int)m, (int)tile, (int)k), "gemm_qkv without a K split: 256 x 256 FA "
-          "tiles with the fused norm (gemm_qkv_direct_ok)");
-    size_t rfl = 0;
-    float* rws = rms_ws_ptr(rms_ws, m, &rfl);
-    rc(jla::gemm(cbf(x), w.data_ptr(), nullptr, m, n, k, MODE_QKV_ID, 0, 0, nullptr, &qa, nullptr, 0, 1, stream(),
-                 (float)rms_eps, (int)tile, rws, rfl),
-       "gemm_qkv");
-    return;
-  }
-  check(ws.has_value(), "gemm_qkv: a K split needs the slab workspace");
-  check_gemm_ws(ws, ksplit, m, n, rms_eps >= 0);
-  rc(jla::gemm(cbf(x), w.data_ptr(), nullptr, m, n, k, MODE_QKV_ID, 0, 0, nullptr, &qa, ptr<float>(*ws), ws->numel(),
-               ksplit, stream(), (float)rms_eps, (int)tile),
-     "gemm_qkv");
+  // without a K split (gemm5 apart): the GEMM's own RoPE / KV-write epilogue; else the reduce kernel's
+  const bool slabs = check_gemm_ws(ws, k, ksplit, m, n, rms_eps >= 0, tile);
+  size_t rfl = 0;
+  float* rws = rms_ws_ptr(rms_ws, m, &rfl);
+  gemm_rc(jla::gemm(cbf(x), w.data_ptr(), nullptr, m, n, k, MODE_QKV, 0, 0, nullptr, &qa,
+                    slabs ? ptr<float>(*ws) : nullptr, slabs ? ws->numel() : 0, ksplit, stream(), (float)rms_eps,
+                    (int)tile, rws, rfl),
+          "gemm_qkv");
 }
 
 void rope_kv_write(Tensor qkv, Tensor table, Tensor positions, Tensor kc, Tensor vc, Tensor slot, int64_t seq_len,
@@ -734,13 +706,13 @@ void linear_tp_residual(int64_t state, Tensor x, Tensor w, int64_t n, int64_t k,
   qa.pack = packed_ptr(hb_pack, m, n, "hb_pack");
   qa.tp = jla::car_device(st);
   // split-K variants (16 / 18 / 26) take the shared decode workspace: only the last arriver of a column group exchanges
-  run_skinny(x, w, n, k, h.data_ptr(), MODE_TPRESID_ID, -1.0, true, true, &qa, variant, ws ? *ws : Tensor(),
+  run_skinny(x, w, n, k, h.data_ptr(), MODE_TPRESID, -1.0, true, true, &qa, variant, ws ? *ws : Tensor(),
              tickets ? *tickets : Tensor(), packed_ptr(x_packed, m, k, "x_packed"));
 }
 
 // Row-parallel tiled projection (decode batches past the GEMV's rows) with the TP all-reduce and residual add in its
 // split-K reduce (gemm.hip gemm_reduce_tp_kernel): h (fp32) += sum over the group of x @ W^T, hb = bf16(h). A split plan
-// (ksplit > 1, or gemm5 tiles 11 / 12) and the shared gemm workspace; one exchange region per 4096 output elements.
+// (ksplit > 1, or a gemm5 tile) and the shared gemm workspace; one exchange region per 4096 output elements.
 void gemm_tp_residual(int64_t state, Tensor x, Tensor w, int64_t n, int64_t k, Tensor h, Tensor hb, int64_t ksplit,
                       Tensor ws, int64_t tile) {
   check_gpu(x, "x");
@@ -755,17 +727,12 @@ void gemm_tp_residual(int64_t state, Tensor x, Tensor w, int64_t n, int64_t k, T
   const int64_t groups = jla::gemm_tp_groups((int)m, (int)n);
   check(groups <= jla::CAR_WG_COUNTERS && groups * jla::TPRES_REGION <= jla::car_max_bytes(st),
         "gemm_tp_residual: the output does not fit the fused exchange buffer");
-  const bool g5 = tile == 11 || tile == 12;
-  check(g5 || ksplit > 1, "gemm_tp_residual: a split-K plan (the exchange lives in the reduce)");
-  if (g5)
-    check_g5_ws(ws, k, ksplit, m, n, false);
-  else
-    check_gemm_ws(ws, ksplit, m, n);
+  check_gemm_ws(ws, k, ksplit, m, n, false, tile);  // (no split, gemm5 apart: no legal plan -- the exchange lives in the reduce)
   jla::QKVArgs qa{};
   qa.tp = jla::car_device(st);
-  rc(jla::gemm(cbf(x), w.data_ptr(), h.data_ptr(), m, n, k, MODE_TPRESID_ID, 1, 1, bf(hb), &qa, ptr<float>(ws),
-               ws.numel(), ksplit, stream(), -1.f, (int)tile, nullptr, 0),
-     "gemm_tp_residual");
+  gemm_rc(jla::gemm(cbf(x), w.data_ptr(), h.data_ptr(), m, n, k, MODE_TPRESID, 1, 1, bf(hb), &qa, ptr<float>(ws),
+                    ws.numel(), ksplit, stream(), -1.f, (int)tile, nullptr, 0),
+          "gemm_tp_residual");
 }
 
 // (value fp32, index int32) all-gathers of the vocab-parallel sampler. mode 0: out_i[n] = index of the first max over
@@ -823,6 +790,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     const int nb = jla::gemm_tail_split((int)tiles_m, (int)n, (int)width, cus > 0 ? (int)cus : jla::gemm_num_cus());
     return std::make_pair((int64_t)nb, nb > 0 ? (n - nb * width + 127) / 128 : (int64_t)0);
   }, py::arg("tiles_m"), py::arg("n"), py::arg("width"), py::arg("cus") = 0);
+  // 0: a legal plan (kernels/gemm_plan.h, the CU count from the current device); else the code gemm() would fail with
+  m.def("gemm_plan_check", [](int64_t m, int64_t n, int64_t k, int64_t mode, bool rms, int64_t ksplit, int64_t tile,
+                              bool has_rms_ws, int64_t n_body) {
+    return jla::gemm_plan_check((int)m, (int)n, (int)k, (int)mode, rms, (int)ksplit, (int)tile, has_rms_ws, (int)n_body);
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("mode"), py::arg("rms"), py::arg("ksplit"), py::arg("tile"),
+     py::arg("has_rms_ws"), py::arg("n_body") = 0);
   m.def("gemm_qkv_direct_ok", [](int64_t m, int64_t tile, int64_t k) {
     return jla::gemm_qkv_direct_ok((int)m, (int)tile, (int)k) != 0;
   });

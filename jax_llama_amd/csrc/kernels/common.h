@@ -12,20 +12,14 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"  // the linear epilogue modes (MODE_*)
+
 typedef uint16_t bf16_t;
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
-// Linear epilogue modes (mirrors ops/__init__.py)
-#define MODE_STORE 0
-#define MODE_RESIDUAL 1
-#define MODE_SWIGLU 2
-#define MODE_QKV 3
-#define MODE_ARGMAX 8
-#define MODE_TPRESID 9  // row-parallel partial -> granule all-reduce over the TP group -> residual (gemv.hip)
 
 // ---- bounds-checked debug build (python build.py --debug-bounds -> jax_llama_amd/_C_dbg*.so, loaded when
 // JLA_DEBUG_BOUNDS=1). The kernels clamp or skip out-of-range indices that come from device state (token ids,

@@ -20,12 +20,11 @@
 #include "common.h"
 #include "gemm4w.h"
 #include "gemm5ws.h"
+#include "gemm_plan.h"
 #include "launchers.h"
 #include "ring.h"
 
 namespace jla {
-
-constexpr int MODE_PARTIAL = 7;  // split-K: fp32 partial tile to the workspace
 
 // ---------------------------------------------------------------------------------------------
 // gemm2: BM x 256 tile (BM = 128 * WM), 4 * WM waves as WM(M) x 4(N), each wave a 128 x 64 sub-tile
@@ -37,14 +36,13 @@ constexpr int MODE_PARTIAL = 7;  // split-K: fp32 partial tile to the workspace
 // (1 KiB = 16 rows x 32 k, lane-linear), so every ds_read_b128 is conflict-free: the packed weights
 // are copied verbatim, x is gathered by per-lane source addresses (16 rows x 64 B per wave-load).
 // Workgroups are remapped so consecutive tiles share an XCD (its own L2), M-grouped by 8.
-constexpr int G2_BN = 256, G2_NBUF = 4, G2_DIST = 3, G2_GROUP_M = 8;
+constexpr int G2_BN = 256, G2_NBUF = 4, G2_GROUP_M = 8;
 #ifdef JLA_GEMM_STAMPS
 // diagnostic build only (tools/debug/gemm_stamps.hip): per-wave cycles of the ping-pong phases
 __device__ unsigned long long g_gemm_stamps[8192 * 8 * 6];
 #endif
 
-// tile index (in the M-grouped launch order) -> (m tile, n tile); shared by the data-parallel launch
-// and the stream-K tail so both walk the same order
+// tile index (in the M-grouped launch order) -> (m tile, n tile)
 JLA_DEV void g2_tile_coords(int pid, int tiles_m, int tiles_n, int& tm, int& tn) {
   const int in_group = G2_GROUP_M * tiles_n;
   const int first_m = (pid / in_group) * G2_GROUP_M;
@@ -58,10 +56,6 @@ JLA_DEV void g2_tile_coords(int pid, int tiles_m, int tiles_n, int& tm, int& tn)
 // takes m-tiles 2wc, 2wc+1 of its row block, 8 v_dot2 per K-tile) and the epilogue scales each output
 // row by rsqrt(mean(x^2) + eps). Split-K: each split stores its partial sums ([split][M] after the
 // fp32 slabs) and the reduce kernel finishes the statistic. No rms_scale launch, no scaled copy of x.
-// SUB = 2 (ping-pong only): each K-tile runs as two half phases per wave group -- [half the tile's
-// LDS-DMA issue + the A/B fragments of m-tiles 0..MT/2-1] -> 16 MFMAs, then [the other half of the issue +
-// the remaining A fragments + the vmcnt wait for tile t+1] -> 16 MFMAs -- so the partner group's MFMA
-// phase hides a shorter load phase (cdna_hip_programming.md T3+T4: the per-phase interleave is the lever).
 // FA (full-line A; 256 x 256 ping-pong only): x is staged in 8-row x 128-B pieces that cover a PAIR of
 // K-tiles (lane l of a piece loads row l>>3, 16-B chunk (l&7) ^ swz(row)), instead of 16-row x 64-B
 // fragment-shaped loads: half the cache lines per LDS-DMA instruction, so half the TA work for x
@@ -70,8 +64,8 @@ JLA_DEV void g2_tile_coords(int pid, int tiles_m, int tiles_n, int& tm, int& tn)
 // gfx950 b128 lane groups. x pairs live in a 3-slot ring (96 KiB), weights in the usual 4-slot K-tile
 // ring (64 KiB); pair p is issued in two halves with K-tiles 2p-4 and 2p-3 (4 LDS-DMA per wave per
 // K-tile, as before), so the vmcnt accounting stays "everything issued two K-tiles back has landed".
-template <int MODE, int WM, int NBUF = G2_NBUF, bool LATE_WAIT = false, bool RMS = false, int MT = 8, int NTW = 4,
-          int SUB = 1, bool FA = false, int FAM = 0>
+template <int MODE, int WM, bool LATE_WAIT = false, bool RMS = false, int MT = 8, int NTW = 4, bool FA = false,
+          int FAM = 0>
 __global__ void __launch_bounds__(256 * WM)
     gemm2_kernel(const bf16_t* __restrict__ x, const u32x4* __restrict__ W, void* __restrict__ out, int M, int N,
                  int K, int accumulate, int out_f32, bf16_t* __restrict__ mirror, int kc, int tiles_m, int tiles_n,
@@ -82,11 +76,11 @@ __global__ void __launch_bounds__(256 * WM)
   constexpr int AF = BM / 16, BF = BN / 16, FR = AF + BF;  // fragments per K-tile
   constexpr int G = FR / NW;                                   // LDS-DMA loads per wave per K-tile
   static_assert(FR % NW == 0, "fragment split");
-  constexpr int DIST = NBUF - 1;
+  constexpr int DIST = G2_NBUF - 1;
   constexpr int A_SLOTS = 3, A_PIECES = BM / 8, A_RING = FA ? A_SLOTS * A_PIECES * 64 : 0;
-  static_assert(!FA || (WM == 2 && MT == 8 && NTW == 4 && SUB == 1 && NBUF == 4 && BF == 2 * NW),
+  static_assert(!FA || (WM == 2 && MT == 8 && NTW == 4 && G2_NBUF == 4 && BF == 2 * NW),
                 "FA: 256 x 256 ping-pong, 2 weight fragments per wave per K-tile");
-  __shared__ u32x4 lds[FA ? A_RING + NBUF * BF * 64 : NBUF * FR * 64];
+  __shared__ u32x4 lds[FA ? A_RING + G2_NBUF * BF * 64 : G2_NBUF * FR * 64];
   u32x4* const bring = lds + A_RING;  // FA: the weight ring follows the x ring
 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -124,15 +118,9 @@ __global__ void __launch_bounds__(256 * WM)
     }
   }
   auto issue = [&](int t) {
-    u32x4* buf = lds + (t % NBUF) * FR * 64;
+    u32x4* buf = lds + (t % G2_NBUF) * FR * 64;
 #pragma unroll
     for (int j = 0; j < G; ++j) glds16(src[j] + (size_t)t * step[j], buf + (w + NW * j) * 64);
-  };
-  // one half of a tile's loads (SUB = 2 issues a tile over two sub-phases)
-  auto issue_half = [&](int t, int h) {
-    u32x4* buf = lds + (t % NBUF) * FR * 64;
-#pragma unroll
-    for (int j = h * (G / 2); j < (h + 1) * (G / 2); ++j) glds16(src[j] + (size_t)t * step[j], buf + (w + NW * j) * 64);
   };
   // FA sources, saddr form: one wave-uniform 64-bit base per operand (advanced by scalar adds) plus a
   // 32-bit per-lane byte offset within the tile (< 15 MB for every Llama shape). x piece 16h + wu + 8j
@@ -170,7 +158,7 @@ __global__ void __launch_bounds__(256 * WM)
     for (int j = 0; j < 2; ++j) issueA1(p, HC, j);
   };
   auto issueB1 = [&](int t, int j) {
-    glds16(baseB + (size_t)t * 1024 + offB[j], bring + (t % NBUF) * BF * 64 + (wu + NW * j) * 64);
+    glds16(baseB + (size_t)t * 1024 + offB[j], bring + (t % G2_NBUF) * BF * 64 + (wu + NW * j) * 64);
   };
   auto issueB = [&](int t) {
 #pragma unroll
@@ -239,65 +227,7 @@ __global__ void __launch_bounds__(256 * WM)
 #else
 #define JLA_STAMP(v)
 #endif
-    if constexpr (SUB == 2) {
-      // Barrier instances per K-tile t (group 0 / group 1 = one instance later): L0 | b | M0 | b | L1 | b | M1 | b.
-      //  RAW: each wave waits for its part of tile t+1 in L1(t) (group 0 before instance 4t+3, group 1 before
-      //       4t+4); tile t+1 is first read in L0(t+1), after instance 4t+4 (group 0) / 4t+5 (group 1).
-      //  WAR: tile t+3 refills tile t-1's buffer from L0(t) on (after instance 4t); the last reads of t-1
-      //       (group 1's L1(t-1)) retired with lgkmcnt(0) before its call of instance 4t.
-      static_assert(MT % 2 == 0 && G % 2 == 0, "SUB=2 splits the m-tiles and the loads in halves");
-      constexpr int MH = MT / 2;
-      for (int t = 0; t < KT; ++t) {
-        const u32x4* buf = lds + (t % NBUF) * FR * 64;
-        u32x4 a[MT], b[NTW];
-        // ---- L0: first half of tile t+3's loads; B fragments and the first half of A
-        if (t + DIST < KT) issue_half(t + DIST, 0);
-#pragma unroll
-        for (int j = 0; j < NTW; ++j) b[j] = buf[(AF + wc * NTW + j) * 64 + lane];
-#pragma unroll
-        for (int i = 0; i < MH; ++i) a[i] = buf[(wr * MT + i) * 64 + lane];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = 0; i < MH; ++i)
-#pragma unroll
-          for (int j = 0; j < NTW; ++j) acc[i][j] = mfma16x16x32(a[i], b[j], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        // ---- L1: second half of the loads; the rest of A; wait for this wave's part of tile t+1
-        if (t + DIST < KT) issue_half(t + DIST, 1);
-#pragma unroll
-        for (int i = MH; i < MT; ++i) a[i] = buf[(wr * MT + i) * 64 + lane];
-        sumsq(buf);
-        {
-          const int after = min(KT - 1, t + DIST) - (t + 1);  // tiles issued after t+1
-          if (after >= 3)
-            wait_vmcnt<3 * G>();
-          else if (after == 2)
-            wait_vmcnt<2 * G>();
-          else if (after == 1)
-            wait_vmcnt<G>();
-          else
-            wait_vmcnt<0>();
-        }
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int i = MH; i < MT; ++i)
-#pragma unroll
-          for (int j = 0; j < NTW; ++j) acc[i][j] = mfma16x16x32(a[i], b[j], acc[i][j]);
-        __builtin_amdgcn_s_setprio(0);
-        asm volatile("" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-      }
-    } else if constexpr (FA) {
+    if constexpr (FA) {
       // FA main loop, unrolled by K-tile pairs so each step's x issue half (and its LDS read chunk) is a
       // compile-time constant. Same phase/barrier structure as the loop below.
       // vmcnt: every load of K-tile t+1 (its weights and both halves of its x pair) was issued at K-tile
@@ -333,7 +263,7 @@ __global__ void __launch_bounds__(256 * WM)
 #endif
         // row r of the tile, chunk c of its 64-deep pair sits at u32x4 r * 8 + (c ^ ((r & 15) >> 1))
         const u32x4* abuf = lds + ((t >> 1) % A_SLOTS) * A_PIECES * 64;
-        const u32x4* bbuf = bring + (t % NBUF) * BF * 64;
+        const u32x4* bbuf = bring + (t % G2_NBUF) * BF * 64;
         const int ab = (wr * MT * 16 + (lane & 15)) * 8 + ((4 * h + (lane >> 4)) ^ ((lane >> 1) & 7));
         u32x4 a[MT], b[NTW];
 #pragma unroll
@@ -440,7 +370,7 @@ __global__ void __launch_bounds__(256 * WM)
 #ifdef JLA_GEMM_STAMPS
       JLA_STAMP(t1) st_iss += t1 - t0; t0 = t1;
 #endif
-      const u32x4* buf = lds + (t % NBUF) * FR * 64;
+      const u32x4* buf = lds + (t % G2_NBUF) * FR * 64;
       u32x4 a[MT], b[NTW];
 #pragma unroll
       for (int j = 0; j < NTW; ++j) b[j] = buf[(AF + wc * NTW + j) * 64 + lane];
@@ -504,7 +434,7 @@ __global__ void __launch_bounds__(256 * WM)
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (t + DIST < KT) issue(t + DIST);  // refills the buffer read at t-1 (retired by the barrier)
-    const u32x4* buf = lds + (t % NBUF) * FR * 64;
+    const u32x4* buf = lds + (t % G2_NBUF) * FR * 64;
     u32x4 a[MT], b[NTW];
 #pragma unroll
     for (int j = 0; j < NTW; ++j) b[j] = buf[(AF + wc * NTW + j) * 64 + lane];
@@ -728,8 +658,8 @@ __global__ void __launch_bounds__(256 * WM)
 // [split][M][N] (+ the fused-RMS partial sums [split][M]) summed by gemm_reduce_kernel, as gemm2's.
 // RMSM (fused RMSNorm statistic): 0 none; 1 summed inside the main loop from the x fragments (split-K partial
 // slabs: per-split sums to ssq_ws); 2 read from rms_inv[M], computed ahead of the GEMM by rms_rowinv_kernel.
-// The epilogue of one gemm4 output tile (every mode; see gemm4_kernel), shared by the data-parallel and the
-// stream-K launches. acc: this wave's finished C^T accumulators; ss: the in-loop RMS partial sums (RMSM 1).
+// The epilogue of one gemm4 output tile (every mode; see gemm4_kernel), shared by the data-parallel, persistent and
+// tail-balanced launches. acc: this wave's finished C^T accumulators; ss: the in-loop RMS partial sums (RMSM 1).
 struct G4Epi {
   void* out;
   int M, N, K, accumulate, out_f32;
@@ -1343,72 +1273,55 @@ int gemm_ksplit(int M, int N, int K) {
   return (KS + kc - 1) / kc;
 }
 
-static int num_cus();
 size_t gemm_workspace_floats(int M, int N, int K) {
   const int ks = gemm_ksplit(M, N, K);
   return ks > 1 ? (size_t)ks * M * (N + 1) : 0;  // slabs + fused-RMS partial sums
 }
 
-// gemm2 tile configurations (the `tile` argument of gemm(); 0 = by M):
-//   1: 256 x 256, 8 waves (two ping-pong rows) of 128 x 64;   2: 128 x 256, 4 waves of 128 x 64;
-//   3: 128 x 128, 8 waves (two ping-pong rows) of 64 x 32 -- 64 KiB of LDS, so two workgroups can share a CU;
-//      for decode shapes with few 256-wide tiles (o / qkv projections) it replaces split-K partial slabs.
-// gemm4 (below): 7 256 x 256; 13 persistent; 14 the weights three K-tiles deep; 16 / 17 256 x 192 / 128 tiles;
-//   18 / 19 tail-balanced (a body of 256 x 192 / 256 x 256 tiles + a tail of 256 x 128 tiles, gemm4t_kernel).
-// gemm5 (gemm5ws.h): 11 / 12.
-static int tile_cfg(int tile, int M) { return tile >= 1 && tile <= 3 ? tile : (M <= 128 ? 2 : 1); }
-static bool use_g4(int tile, int M, int K);
-// gemm4 on narrower tiles, both with the weights three K-tiles deep (W3; the two-slot forms, tiles 10 / 15, were
-// never picked by the tuner at a bench shape and were removed in round 6):
-constexpr int G4N6D_TILE = 16;  // 256 x 192 tiles (g4n_mainloop<6, W3>)
-constexpr int G4ND_TILE = 17;   // 256 x 128 tiles (g4n_mainloop<4, W3>)
-// tail-balanced gemm4 (gemm4t_kernel): a body of 256 x 192 / 256 x 256 tiles, then one region of 256 x 128 tiles
-constexpr int G4T6_TILE = 18;  // body 192 + tail 128
-constexpr int G4T8_TILE = 19;  // body 256 + tail 128
-static bool is_g4t(int tile) { return tile == G4T6_TILE || tile == G4T8_TILE; }
-int gemm_tail_width(int tile) { return tile == G4T6_TILE ? 192 : (tile == G4T8_TILE ? 256 : 0); }
-
-// The body n-tile count of the tail-balanced plan for tiles_m m-tiles x N columns, body tiles `width` (192 / 256)
-// columns wide, on `cus` CUs; the tail is the remaining columns in 128-wide tiles. Minimises the modelled time
-// rounds x tile width, ceil(tm * n_body / cus) * width + ceil(tm * n_tail / cus) * 128 * (1 + 1/16): the narrow tile
-// moves 1.5x / 2x the operand bytes per MFMA of the 192 / 256 one, which the 1/16 stands for. Ties go to regions that
-// are multiples of 8 workgroups (the XCD count), then to the wider body. 0: no split beats the uniform `width` grid
-// (N already fills whole rounds, or the tail would cost a round of its own for nothing).
-int gemm_tail_split(int tiles_m, int N, int width, int cus) {
-  if (tiles_m <= 0 || N <= 0 || cus <= 0 || (width != 192 && width != 256)) return 0;
-  auto rounds = [&](long long wgs) { return (wgs + cus - 1) / cus; };
-  auto tail_tiles = [&](int nb) { return (N - nb * width + 127) / 128; };
-  auto aligned = [&](int nb) { return (tiles_m * nb) % 8 == 0 && (tiles_m * tail_tiles(nb)) % 8 == 0; };
-  long long best = rounds((long long)tiles_m * ((N + width - 1) / width)) * width * 16;  // the uniform grid
-  int best_nb = 0;
-  for (int nb = (N - 1) / width; nb >= 1; --nb) {
-    const long long cost =
-        rounds((long long)tiles_m * nb) * width * 16 + rounds((long long)tiles_m * tail_tiles(nb)) * 128 * 17;
-    if (cost < best || (best_nb != 0 && cost == best && aligned(nb) && !aligned(best_nb))) {
-      best = cost;
-      best_nb = nb;
-    }
+static int num_cus() {
+  static int cus = 0;
+  if (cus == 0) {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
+      cus = prop.multiProcessorCount;
+    if (cus <= 0) cus = 256;
   }
-  return best_nb;
+  return cus;
 }
+int gemm_num_cus() { return num_cus(); }
+
+// The launchers below run a legal plan (gemm_plan.h: the tile ids, the kernel family of each and every rule): they
+// check nothing themselves.
+static bool g_g4_default = true;  // tile 0 resolves to gemm4 where it applies (tools switch it off for A/B)
+void gemm_set_g4_default(int on) { g_g4_default = on != 0; }
 int gemm_qkv_direct_ok(int M, int tile, int K) {
-  return ((tile == 0 || tile == 1) && tile_cfg(tile, M) == 1) || use_g4(tile, M, K) ||
-         (tile == G4N6D_TILE && (K & 63) == 0);
+  const GemmPlanResult r = gemm_plan(M, 16, K, MODE_QKV, true, 1, tile, true, 0, 0, g_g4_default);
+  return r.rc == 0 && !r.plan.reduce;
+}
+int gemm_plan_check(int M, int N, int K, int mode, int rms, int ksplit, int tile, int has_rms_ws, int n_body) {
+  return gemm_plan(M, N, K, mode, rms != 0, ksplit, tile, has_rms_ws != 0, n_body, num_cus(), g_g4_default).rc;
 }
 
-// gemm4 (tile config 7; the default for tile 0 once g_g4_default is set): the 4-wave 256 x 256 kernel of gemm4w.h.
-// Needs K % 64 == 0; data-parallel or plain split-K (MODE_PARTIAL + reduce kernel) only -- the stream-K tail,
-// hybrid and in-kernel fixup plans stay on gemm2.
-constexpr int G4_TILE = 7;
-static bool g_g4_default = true;
-void gemm_set_g4_default(int on) { g_g4_default = on != 0; }
-constexpr int G4P_TILE = 13;  // persistent gemm4 (gemm4p_kernel)
-// tile config 14: gemm4 with the weight operand three K-tiles deep (g4_mainloop W3, 160 KiB of LDS) -- for the small-M
-// plans whose weights stream from HBM with few tiles sharing them
-constexpr int G4D_TILE = 14;
-static bool use_g4(int tile, int M, int K) {
-  return (K & 63) == 0 &&
-         (tile == G4_TILE || tile == G4P_TILE || tile == G4D_TILE || (tile == 0 && g_g4_default && M > 128));
+// One launch of a tile kernel: the operands and epilogue arguments every family takes.
+struct GemmArgs {
+  const bf16_t* x;
+  const u32x4* w;
+  void* out;
+  int M, N, K, accumulate, out_f32;
+  bf16_t* mirror;
+  float rms_eps;
+  float* ssq;     // K split: the per-split sums of squares of the fused norm (behind the slabs)
+  float* rms_ws;  // NORM_PRECOMPUTED: the row statistic's scratch
+  QKVArgs qa;
+  hipStream_t s;
+};
+
+// NORM_PRECOMPUTED: the row statistic into the scratch, ahead of the GEMM (inv: what the kernel reads; null otherwise).
+// False: that launch failed.
+static bool g4_row_stat(const GemmArgs& a, const GemmPlan& p, const float*& inv) {
+  inv = p.norm == NORM_PRECOMPUTED ? a.rms_ws : nullptr;
+  return inv == nullptr || rms_rowinv(a.x, a.rms_ws, a.M, a.K, a.rms_eps, a.s) == 0;  // (K % 8 == 0 always holds here)
 }
 
 // Tile rasterisation: the launch order walks groups of gm m-tiles across every n-tile (g4_tile_coords), so the 32
@@ -1417,197 +1330,176 @@ static bool use_g4(int tile, int M, int K) {
 // gate_up -5 / 0 %, down -5 / -6 % (profiles/r5_gemm4_group_m.jsonl). gemm_set_g4_group pins another (tools).
 static int g_g4_group = 0;
 void gemm_set_g4_group(int gm) { g_g4_group = gm; }
-static int g4_group_m(int tiles_m, int tiles_n, int K) {
-  (void)tiles_n, (void)K;
+static int g4_group_m(int tiles_m) {
   const int gm = g_g4_group > 0 ? g_g4_group : 4;
   return gm < tiles_m ? gm : tiles_m;
 }
 static int g_g5_diag = 0;  // tools only (gemm5ws.h diag bits 1-16; gemm4 store ablations 64 / 128: wrong results)
-template <int MODE, int NJ = 8>
-static void launch_g4(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate, int out_f32,
-                      bf16_t* mirror, int ksplit, float rms_eps, float* ssq, hipStream_t s, const QKVArgs& qa,
-                      float* rms_ws = nullptr, bool persistent = false, bool deep = false) {
-  const int tm = (M + G4_BM - 1) / G4_BM, tn = (N + 32 * NJ - 1) / (32 * NJ);
-  const int KS64 = K >> 6, kc = (KS64 + ksplit - 1) / ksplit;  // splits past the end run no K-tile (zero slabs)
-  const bool rms = MODE != MODE_RESIDUAL && rms_eps >= 0.f;
-  const int grid = tm * tn * ksplit;
-  const int gm = g4_group_m(tm, tn, K);
-  if constexpr (NJ == 8 && MODE != MODE_PARTIAL && MODE != MODE_ARGMAX) {
-    if (persistent && ksplit == 1) {  // tile config 13: one workgroup per CU over every tile
-      const int pg = min(grid, num_cus());
-      if (rms && rms_ws != nullptr) {
-        if (rms_rowinv(x, rms_ws, M, K, rms_eps, s) != 0) return;
-        gemm4p_kernel<MODE, 2><<<pg, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, tn, rms_eps, qa,
-                                                  rms_ws, gm);
-      } else if (rms) {
-        gemm4p_kernel<MODE, 1><<<pg, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, tn, rms_eps, qa,
-                                                  nullptr, gm);
-      } else {
-        gemm4p_kernel<MODE, 0><<<pg, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, tn, rms_eps, qa,
-                                                  nullptr, gm);
-      }
-      return;
-    }
-  }
-  if constexpr (NJ != 8) {  // 256 x 128 / 192 tiles (deep W only): the statistic precomputed (callers guarantee rms_ws,
-    //                         no K split)
-    if (rms && rms_ws != nullptr && ksplit == 1 && MODE != MODE_PARTIAL) {
-      if (rms_rowinv(x, rms_ws, M, K, rms_eps, s) != 0) return;
-      gemm4_kernel<MODE, 2, NJ, 0, true><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm,
-                                                              tn, rms_eps, ssq, qa, rms_ws, gm);
-    } else if (!rms) {
-      gemm4_kernel<MODE, 0, NJ, 0, true><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm,
-                                                              tn, rms_eps, ssq, qa, nullptr, gm);
-    }
-    return;
-  }
-  if constexpr (MODE == MODE_STORE) {  // ablation instances (tools only; wrong results)
-    if (!rms && (g_g5_diag & 192)) {
-      if ((g_g5_diag & 192) == 64)
-        gemm4_kernel<MODE, 0, 8, 1><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm, tn,
-                                                        rms_eps, ssq, qa, nullptr, gm);
-      else if ((g_g5_diag & 192) == 128)
-        gemm4_kernel<MODE, 0, 8, 2><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm, tn,
-                                                        rms_eps, ssq, qa, nullptr, gm);
-      else
-        gemm4_kernel<MODE, 0, 8, 3><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm, tn,
-                                                        rms_eps, ssq, qa, nullptr, gm);
-      return;
-    }
-  }
-#define JLA_G4(R, INV)                                                                                             \
-  if (deep)                                                                                                         \
-    gemm4_kernel<MODE, R, 8, 0, true><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm, \
-                                                           tn, rms_eps, ssq, qa, INV, gm);                          \
-  else                                                                                                              \
-    gemm4_kernel<MODE, R><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm, tn, rms_eps, \
-                                               ssq, qa, INV, gm)
-  if (rms && rms_ws != nullptr && ksplit == 1 && MODE != MODE_PARTIAL) {
-    if (rms_rowinv(x, rms_ws, M, K, rms_eps, s) != 0) return;  // (K % 8 == 0 always holds here)
-    JLA_G4(2, rms_ws);
-  } else if (rms) {
-    JLA_G4(1, nullptr);
+void gemm5_set_diag(int d) { g_g5_diag = d; }
+
+// gemm4 on 256 x 32 NJ tiles; NJ = 6 / 4: the weights three K-tiles deep, the norm as the precomputed statistic only
+template <int MODE, int NJ>
+static void launch_g4(const GemmArgs& a, const GemmPlan& p) {
+  const int tm = (a.M + G4_BM - 1) / G4_BM, tn = (a.N + 32 * NJ - 1) / (32 * NJ);
+  const int grid = tm * tn * p.ksplit, gm = g4_group_m(tm);
+  const float* inv;
+  if (!g4_row_stat(a, p, inv)) return;
+#define JLA_G4(R, DIAG, DEEP)                                                                                       \
+  gemm4_kernel<MODE, R, NJ, DIAG, DEEP><<<grid, 256, 0, a.s>>>(a.x, a.w, a.out, a.M, a.N, a.K, a.accumulate, a.out_f32, \
+                                                               a.mirror, p.kc, tm, tn, a.rms_eps, a.ssq, a.qa, inv, gm)
+  if constexpr (NJ != 8) {
+    if (inv)
+      JLA_G4(2, 0, true);
+    else
+      JLA_G4(0, 0, true);
   } else {
-    JLA_G4(0, nullptr);
+    if constexpr (MODE == MODE_STORE) {  // ablation instances (tools only; wrong results)
+      if (p.norm == NORM_NONE && (g_g5_diag & 192)) {
+        if ((g_g5_diag & 192) == 64)
+          JLA_G4(0, 1, false);
+        else if ((g_g5_diag & 192) == 128)
+          JLA_G4(0, 2, false);
+        else
+          JLA_G4(0, 3, false);
+        return;
+      }
+    }
+    if (p.norm == NORM_PRECOMPUTED) {
+      if (p.deep) JLA_G4(2, 0, true); else JLA_G4(2, 0, false);
+    } else if (p.norm == NORM_INLOOP) {
+      if (p.deep) JLA_G4(1, 0, true); else JLA_G4(1, 0, false);
+    } else {
+      if (p.deep) JLA_G4(0, 0, true); else JLA_G4(0, 0, false);
+    }
   }
 #undef JLA_G4
 }
 
-// tile configs 18 / 19: n_body body n-tiles of 32 NJB columns, the rest in 128-wide tiles (gemm() has checked the
-// plan: no K split, 0 < n_body * 32 NJB < N, the norm statistic's scratch)
-template <int MODE, int NJB>
-static void launch_g4t(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate, int out_f32,
-                       bf16_t* mirror, float rms_eps, hipStream_t s, float* rms_ws, int n_body) {
-  const int tm = (M + G4_BM - 1) / G4_BM, nt = (N - n_body * 32 * NJB + 127) / 128;
-  const bool rms = MODE != MODE_RESIDUAL && rms_eps >= 0.f;
-  const int grid = tm * (n_body + nt);
-  const int gm = g4_group_m(tm, n_body, K);
-  if (rms) {
-    if (rms_ws == nullptr || rms_rowinv(x, rms_ws, M, K, rms_eps, s) != 0) return;
-    gemm4t_kernel<MODE, 2, NJB><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, n_body, nt,
-                                                     rms_eps, rms_ws, gm);
-  } else {
-    gemm4t_kernel<MODE, 0, NJB><<<grid, 256, 0, s>>>(x, w, out, M, N, K, accumulate, out_f32, mirror, tm, n_body, nt,
-                                                     rms_eps, nullptr, gm);
-  }
-}
-
+// persistent gemm4: one workgroup per CU over every 256 x 256 tile
 template <int MODE>
-static void launch_g2(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate, int out_f32,
-                      bf16_t* mirror, int kc, int ksplit, float rms_eps, float* ssq, int tile, hipStream_t s,
-                      const QKVArgs& qa = QKVArgs{}, float* rms_ws = nullptr, int n_body = 0) {
-  if constexpr (MODE == MODE_STORE || MODE == MODE_RESIDUAL || MODE == MODE_SWIGLU) {
-    if (is_g4t(tile)) {
-      if (tile == G4T6_TILE)
-        launch_g4t<MODE, 6>(x, w, out, M, N, K, accumulate, out_f32, mirror, rms_eps, s, rms_ws, n_body);
-      else
-        launch_g4t<MODE, 8>(x, w, out, M, N, K, accumulate, out_f32, mirror, rms_eps, s, rms_ws, n_body);
-      return;
-    }
-  }
-  if constexpr (MODE != MODE_QKV && MODE != MODE_ARGMAX) {
-    if (tile == G4ND_TILE && (K & 63) == 0) {
-      launch_g4<MODE, 4>(x, w, out, M, N, K, accumulate, out_f32, mirror, ksplit, rms_eps, ssq, s, qa, rms_ws, false,
-                         true);
-      return;
-    }
-  }
-  // tile config 16: 256 x 192 tiles -- Llama-3-8B qkv (N = 6144) at M = 2048 is 8 x 32 = 256 tiles, one per CU, where
-  // the 256 x 256 grid has 192 (0.75 of a wave); the QKV epilogue included
-  if constexpr (MODE != MODE_ARGMAX) {
-    if (tile == G4N6D_TILE && (K & 63) == 0) {
-      launch_g4<MODE, 6>(x, w, out, M, N, K, accumulate, out_f32, mirror, ksplit, rms_eps, ssq, s, qa, rms_ws, false,
-                         true);
-      return;
-    }
-  }
-  if (use_g4(tile, M, K)) {
-    // persistent for the residual epilogue at prefill sizes: o / down at M = 32768 3.5 / 2.4 % faster (the CUs'
-    // fp32 read-modify-write bursts desynchronise); the store / SwiGLU / QKV epilogues lose 1.5-3.6 % that way
-    // (profiles/r5_gemm4_persistent_ab.jsonl)
-    const bool persist = tile == G4P_TILE || (MODE == MODE_RESIDUAL && tile == 0 && ksplit == 1 && M >= 4096);
-    launch_g4<MODE>(x, w, out, M, N, K, accumulate, out_f32, mirror, ksplit, rms_eps, ssq, s, qa, rms_ws, persist,
-                    tile == G4D_TILE);
-    return;
-  }
-  const int cfg = tile_cfg(tile, M);
-  const int bm = cfg == 1 ? 256 : 128, bn = cfg == 3 ? 128 : 256;
-  const int tm = (M + bm - 1) / bm, tn = (N + bn - 1) / bn;
-  const int grid = tm * tn * ksplit;
-#define JLA_G2S(WMV, NB, LATE, R, MTV, NTV, SB)                                                             \
-  gemm2_kernel<MODE, WMV, NB, LATE, R, MTV, NTV, SB><<<grid, 256 * WMV, 0, s>>>(                            \
-      x, w, out, M, N, K, accumulate, out_f32, mirror, kc, tm, tn, rms_eps, ssq, qa)
-#define JLA_G2(WMV, NB, LATE, R, MTV, NTV) JLA_G2S(WMV, NB, LATE, R, MTV, NTV, 1)
-#define JLA_G2FA(R, FM)                                                                                      \
-  gemm2_kernel<MODE, 2, 4, true, R, 8, 4, 1, true, FM><<<grid, 512, 0, s>>>(x, w, out, M, N, K, accumulate,     \
-                                                                           out_f32, mirror, kc, tm, tn, rms_eps, ssq, qa)
-  if constexpr (MODE == MODE_QKV) {  // the direct RoPE / KV-write epilogue: the default 256 x 256 FA pipeline only
-    JLA_G2FA(true, 2);
-  } else {
-  const bool rms = MODE != MODE_RESIDUAL && rms_eps >= 0.f;
-  if constexpr (MODE != MODE_RESIDUAL) {
-    if (rms) {  // fused RMSNorm statistic (default pipeline variant only)
-      if (cfg == 2)
-        JLA_G2(1, 4, false, true, 8, 4);
-      else if (cfg == 3)
-        JLA_G2(2, 4, true, true, 4, 2);
-      else
-        JLA_G2FA(true, 2);
-      return;
-    }
-  }
-  if (cfg == 2)
-    JLA_G2(1, 4, false, false, 8, 4);
-  else if (cfg == 3)
-    JLA_G2(2, 4, true, false, 4, 2);
+static void launch_g4p(const GemmArgs& a, const GemmPlan& p) {
+  const int tm = (a.M + G4_BM - 1) / G4_BM, tn = (a.N + G4_BN - 1) / G4_BN;
+  const int grid = min(tm * tn, num_cus()), gm = g4_group_m(tm);
+  const float* inv;
+  if (!g4_row_stat(a, p, inv)) return;
+#define JLA_G4P(R)                                                                                                  \
+  gemm4p_kernel<MODE, R><<<grid, 256, 0, a.s>>>(a.x, a.w, a.out, a.M, a.N, a.K, a.accumulate, a.out_f32, a.mirror, tm, \
+                                                tn, a.rms_eps, a.qa, inv, gm)
+  if (p.norm == NORM_PRECOMPUTED)
+    JLA_G4P(2);
+  else if (p.norm == NORM_INLOOP)
+    JLA_G4P(1);
   else
-    JLA_G2FA(false, 2);
-  }
-#undef JLA_G2FA
-#undef JLA_G2
-#undef JLA_G2S
+    JLA_G4P(0);
+#undef JLA_G4P
 }
 
+// tail-balanced gemm4: p.n_body body n-tiles of 32 NJB columns, the rest in 128-wide tiles
+template <int MODE, int NJB>
+static void launch_g4t(const GemmArgs& a, const GemmPlan& p) {
+  const int tm = (a.M + G4_BM - 1) / G4_BM, nt = (a.N - p.n_body * 32 * NJB + 127) / 128;
+  const int grid = tm * (p.n_body + nt), gm = g4_group_m(tm);
+  const float* inv;
+  if (!g4_row_stat(a, p, inv)) return;
+  if (inv)
+    gemm4t_kernel<MODE, 2, NJB><<<grid, 256, 0, a.s>>>(a.x, a.w, a.out, a.M, a.N, a.K, a.accumulate, a.out_f32,
+                                                       a.mirror, tm, p.n_body, nt, a.rms_eps, inv, gm);
+  else
+    gemm4t_kernel<MODE, 0, NJB><<<grid, 256, 0, a.s>>>(a.x, a.w, a.out, a.M, a.N, a.K, a.accumulate, a.out_f32,
+                                                       a.mirror, tm, p.n_body, nt, a.rms_eps, nullptr, gm);
+}
+
+// gemm2 tile configs 1 / 2 / 3 (p.family). The direct QKV and the argmax epilogues exist on the 256 x 256 tile only.
 template <int MODE>
-static void launch_tiled(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int accumulate,
-                         int out_f32, bf16_t* mirror, int kc, int ksplit, float rms_eps, float* ssq, int tile,
-                         hipStream_t s, float* rms_ws = nullptr, int n_body = 0) {
-  launch_g2<MODE>(x, w, out, M, N, K, accumulate, out_f32, mirror, kc, ksplit, rms_eps, ssq, tile, s, QKVArgs{},
-                  rms_ws, n_body);
+static void launch_g2(const GemmArgs& a, const GemmPlan& p) {
+  const int cfg = p.family;
+  const int bm = cfg == 1 ? 256 : 128, bn = cfg == 3 ? 128 : 256;
+  const int tm = (a.M + bm - 1) / bm, tn = (a.N + bn - 1) / bn;
+  const int grid = tm * tn * p.ksplit;
+#define JLA_G2(WMV, LATE, R, MTV, NTV, FA, FM)                                                                     \
+  gemm2_kernel<MODE, WMV, LATE, R, MTV, NTV, FA, FM><<<grid, 256 * WMV, 0, a.s>>>(                                 \
+      a.x, a.w, a.out, a.M, a.N, a.K, a.accumulate, a.out_f32, a.mirror, p.kc, tm, tn, a.rms_eps, a.ssq, a.qa)
+#define JLA_G2_CFG(R)                        \
+  if (cfg == 2)                              \
+    JLA_G2(1, false, R, 8, 4, false, 0);     \
+  else if (cfg == 3)                         \
+    JLA_G2(2, true, R, 4, 2, false, 0);      \
+  else                                       \
+    JLA_G2(2, true, R, 8, 4, true, 2)
+  [[maybe_unused]] const bool rms = p.norm != NORM_NONE;  // the statistic summed in the main loop
+  if constexpr (MODE == MODE_QKV) {
+    JLA_G2(2, true, true, 8, 4, true, 2);
+  } else if constexpr (MODE == MODE_ARGMAX) {
+    if (rms)
+      JLA_G2(2, true, true, 8, 4, true, 2);
+    else
+      JLA_G2(2, true, false, 8, 4, true, 2);
+  } else if constexpr (MODE == MODE_RESIDUAL) {
+    JLA_G2_CFG(false);
+  } else {
+    if (rms) {
+      JLA_G2_CFG(true);
+    } else {
+      JLA_G2_CFG(false);
+    }
+  }
+#undef JLA_G2_CFG
+#undef JLA_G2
 }
 
-static int g_num_cus = 0;
-static int num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      g_num_cus = prop.multiProcessorCount;
-    if (g_num_cus <= 0) g_num_cus = 256;
-  }
-  return g_num_cus;
+// gemm5: the weight-streaming partial kernel (a.out: the slab workspace); the reduce kernel follows for any split
+static void launch_g5(const GemmArgs& a, const GemmPlan& p) {
+  const int mt = a.M <= 128 ? 8 : 16, rows = 16 * mt, ntw = p.nj;
+  const int tiles_m = (a.M + rows - 1) / rows, tiles_n = (a.N + 64 * ntw - 1) / (64 * ntw);
+  const int grid = tiles_m * tiles_n * p.ksplit;
+#define JLA_G5(MTV, NTV)                                                                                            \
+  gemm5_partial_kernel<MTV, NTV><<<grid, 256, 0, a.s>>>(a.x, a.w, static_cast<float*>(a.out), a.M, a.N, a.K, p.kc, \
+                                                        tiles_m, tiles_n, a.ssq, g_g5_diag)
+  if (mt == 8 && ntw == 4)
+    JLA_G5(8, 4);
+  else if (mt == 8)
+    JLA_G5(8, 2);
+  else if (ntw == 4)
+    JLA_G5(16, 4);
+  else
+    JLA_G5(16, 2);
+#undef JLA_G5
 }
-int gemm_num_cus() { return num_cus(); }
+
+// the tile kernel of the plan, epilogue MODE (MODE_PARTIAL: slabs for the reduce kernel)
+template <int MODE>
+static void launch_plan(const GemmArgs& a, const GemmPlan& p) {
+  constexpr bool PLAIN = MODE == MODE_STORE || MODE == MODE_RESIDUAL || MODE == MODE_SWIGLU;
+  switch (p.family) {
+    case GEMM2_256x256:
+    case GEMM2_128x256:
+    case GEMM2_128x128: launch_g2<MODE>(a, p); break;
+    case GEMM4:
+      if (p.nj == 8) launch_g4<MODE, 8>(a, p);
+      if constexpr (MODE != MODE_ARGMAX) {
+        if (p.nj == 6) launch_g4<MODE, 6>(a, p);
+      }
+      if constexpr (PLAIN || MODE == MODE_PARTIAL) {
+        if (p.nj == 4) launch_g4<MODE, 4>(a, p);
+      }
+      break;
+    case GEMM4_PERSISTENT:
+      if constexpr (PLAIN || MODE == MODE_QKV) launch_g4p<MODE>(a, p);
+      break;
+    case GEMM4_TAIL:
+      if constexpr (PLAIN) {
+        if (p.nj == 6)
+          launch_g4t<MODE, 6>(a, p);
+        else
+          launch_g4t<MODE, 8>(a, p);
+      }
+      break;
+    case GEMM5:
+      if constexpr (MODE == MODE_PARTIAL) launch_g5(a, p);
+      break;
+    case GEMM_NONE: break;
+  }
+}
 
 // the split-K reduce + epilogue launch over [ksplit][M][N] partial slabs (+ [ksplit][M] sums of squares, fused norm)
 static int launch_reduce(const float* ws, int ksplit, void* out, int M, int N, int K, int mode, int accumulate,
@@ -1646,115 +1538,44 @@ static int launch_reduce(const float* ws, int ksplit, void* out, int M, int N, i
   return 0;
 }
 
-// gemm5 (tile 11: 4 n-tiles per wave, 256-column workgroups; tile 12: 2 n-tiles, 128 columns): the weight-streaming
-// split-K main loop (gemm5ws.h), then the reduce kernel runs the epilogue (even without a K split)
-void gemm5_set_diag(int d) { g_g5_diag = d; }
-int gemm5_ksplit(int K, int ksplit) {  // the effective split count over 64-deep K-stages
-  const int KS64 = K >> 6;
-  if (ksplit < 1) ksplit = 1;
-  const int kc = (KS64 + ksplit - 1) / ksplit;
-  return (KS64 + kc - 1) / kc;
-}
-static int launch_g5(const bf16_t* x, const u32x4* w, void* out, int M, int N, int K, int mode, int accumulate,
-                     int out_f32, bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit,
-                     float rms_eps, int tile, hipStream_t s) {
-  if ((K & 63) || (N & 15) || M <= 0) return -1;
-  if (mode == MODE_SWIGLU && (N & 31)) return -1;
-  if (mode == MODE_QKV && !qkv) return -1;
-  const bool rms = rms_eps >= 0.f && mode != MODE_RESIDUAL;
-  const int KS64 = K >> 6;
-  ksplit = gemm5_ksplit(K, ksplit);
-  const int kc = (KS64 + ksplit - 1) / ksplit;
-  const size_t need = (size_t)ksplit * M * N + (rms ? (size_t)ksplit * M : 0);
-  if (ws == nullptr || ws_floats < need) return -3;
-  float* ssq = rms ? ws + (size_t)ksplit * M * N : nullptr;
-  const int mt = M <= 128 ? 8 : 16, rows = 16 * mt;
-  const int ntw = tile == G5_TILE ? 4 : 2;
-  const int tiles_m = (M + rows - 1) / rows, tiles_n = (N + 64 * ntw - 1) / (64 * ntw);
-  const int grid = tiles_m * tiles_n * ksplit;
-  if (mt == 8 && ntw == 4)
-    gemm5_partial_kernel<8, 4><<<grid, 256, 0, s>>>(x, w, ws, M, N, K, kc, tiles_m, tiles_n, ssq, g_g5_diag);
-  else if (mt == 8)
-    gemm5_partial_kernel<8, 2><<<grid, 256, 0, s>>>(x, w, ws, M, N, K, kc, tiles_m, tiles_n, ssq, g_g5_diag);
-  else if (ntw == 4)
-    gemm5_partial_kernel<16, 4><<<grid, 256, 0, s>>>(x, w, ws, M, N, K, kc, tiles_m, tiles_n, ssq, g_g5_diag);
-  else
-    gemm5_partial_kernel<16, 2><<<grid, 256, 0, s>>>(x, w, ws, M, N, K, kc, tiles_m, tiles_n, ssq, g_g5_diag);
-  JLA_CHECK_LAUNCH();
-  return launch_reduce(ws, ksplit, out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ssq, rms_eps, s);
-}
-
 int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mode, int accumulate, int out_f32,
          bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit, hipStream_t s,
          float rms_eps, int tile, float* rms_ws, size_t rms_ws_floats, int n_body) {
-  if (tile == G5_TILE || tile == G5_TILE + 1) {
-    if (mode == MODE_ARGMAX || (rms_eps >= 0.f && (mode == MODE_RESIDUAL || mode == MODE_TPRESID))) return -1;
-    return launch_g5(x, static_cast<const u32x4*>(W), out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ws,
-                     ws_floats, ksplit, rms_eps, tile, s);
-  }
-  if (rms_ws != nullptr && rms_ws_floats < (size_t)M) rms_ws = nullptr;  // too small: the in-loop statistic
-  if (tile == G4ND_TILE &&
-      ((K & 63) || (mode == MODE_QKV && ksplit <= 1) || mode == MODE_ARGMAX ||
-       (rms_eps >= 0.f && mode != MODE_RESIDUAL && (ksplit > 1 || rms_ws == nullptr))))
-    return -1;  // the 256 x 128 plan: no QKV / argmax epilogue, the fused norm only precomputed without a K split
-  if (M <= 0) return 0;
-  if ((N & 15) || (K & 31)) return -1;
-  if (mode == MODE_SWIGLU && (N & 31)) return -1;
-  const bool rms = rms_eps >= 0.f;
-  if (rms && mode == MODE_RESIDUAL) return -5;  // caller pre-scales x instead
-  if (mode == MODE_QKV && !qkv) return -1;
-  const int KS = K >> 5;
-  if (ksplit < 1) ksplit = 1;
-  const int kc = (KS + ksplit - 1) / ksplit;
-  ksplit = (KS + kc - 1) / kc;
-  if (mode == MODE_TPRESID && (ksplit == 1 || rms)) return -1;  // the exchange lives in the split-K reduce
-  // qkv without a K split: the RoPE / KV-write epilogue of the default FA pipeline (256 x 256 tiles, fused norm)
-  if (mode == MODE_QKV && ksplit == 1 && !(gemm_qkv_direct_ok(M, tile, K) && rms)) return -1;
-  // the 256 x 128 / 192 tiles take the fused norm only as the precomputed statistic without a K split (launch_g4
-  // would otherwise launch nothing)
-  if ((tile == G4ND_TILE || tile == G4N6D_TILE) && rms &&
-      (ksplit > 1 || rms_ws == nullptr))
-    return -6;
-  // the tail-balanced plans: store / residual / SwiGLU without a K split, the norm as the precomputed statistic;
-  // n_body > 0 pins the body n-tile count (tests), else the modelled best split -- none (-7) where the uniform grid
-  // already fills whole rounds
-  if (is_g4t(tile)) {
-    if ((K & 63) || ksplit > 1 || (mode != MODE_STORE && mode != MODE_RESIDUAL && mode != MODE_SWIGLU)) return -1;
-    if (rms && rms_ws == nullptr) return -6;
-    const int wb = gemm_tail_width(tile);
-    if (n_body <= 0) n_body = gemm_tail_split((M + G4_BM - 1) / G4_BM, N, wb, num_cus());
-    if (n_body <= 0 || (long long)n_body * wb >= N) return -7;
-  }
+  const bool has_rms_ws = rms_ws != nullptr && rms_ws_floats >= (size_t)M;  // too small: the in-loop statistic
+  const GemmPlanResult r =
+      gemm_plan(M, N, K, mode, rms_eps >= 0.f, ksplit, tile, has_rms_ws, n_body, num_cus(), g_g4_default);
+  const GemmPlan& p = r.plan;
+  if (r.rc != 0 || p.family == GEMM_NONE) return r.rc;
+  if (mode == MODE_ARGMAX || (mode == MODE_QKV && !qkv)) return -1;  // (gemm_argmax()'s epilogue)
   const u32x4* w = static_cast<const u32x4*>(W);
-  if (ksplit == 1) {
+  if (!p.reduce) {  // the epilogue in the tile kernel
+    GemmArgs a{x, w, out, M, N, K, accumulate, out_f32, nullptr, rms_eps, nullptr, rms_ws, QKVArgs{}, s};
     switch (mode) {
       case MODE_QKV:
-        launch_g2<MODE_QKV>(x, w, nullptr, M, N, K, 0, 0, nullptr, kc, 1, rms_eps, nullptr, tile, s, *qkv, rms_ws);
+        a.out = nullptr, a.accumulate = a.out_f32 = 0, a.qa = *qkv;
+        launch_plan<MODE_QKV>(a, p);
         break;
-      case MODE_STORE:
-        launch_tiled<MODE_STORE>(x, w, out, M, N, K, accumulate, out_f32, nullptr, kc, 1, rms_eps, nullptr, tile, s,
-                                 rms_ws, n_body);
-        break;
+      case MODE_STORE: launch_plan<MODE_STORE>(a, p); break;
       case MODE_RESIDUAL:
-        launch_tiled<MODE_RESIDUAL>(x, w, out, M, N, K, accumulate, 1, mirror, kc, 1, -1.f, nullptr, tile, s, nullptr,
-                                    n_body);
+        a.out_f32 = 1, a.mirror = mirror, a.rms_eps = -1.f;
+        launch_plan<MODE_RESIDUAL>(a, p);
         break;
       case MODE_SWIGLU:
-        launch_tiled<MODE_SWIGLU>(x, w, out, M, N, K, accumulate, 0, nullptr, kc, 1, rms_eps, nullptr, tile, s,
-                                  rms_ws, n_body);
+        a.out_f32 = 0;
+        launch_plan<MODE_SWIGLU>(a, p);
         break;
       default: return -1;
     }
     JLA_CHECK_LAUNCH();
     return 0;
   }
-  // workspace: [ksplit][M][N] fp32 partial slabs, then (fused RMS) [ksplit][M] partial sums of squares
-  const size_t need = (size_t)ksplit * M * N + (rms ? (size_t)ksplit * M : 0);
-  if ((N & 3) || ws == nullptr || ws_floats < need) return -3;
-  float* ssq = rms ? ws + (size_t)ksplit * M * N : nullptr;
-  launch_tiled<MODE_PARTIAL>(x, w, ws, M, N, K, 0, 1, nullptr, kc, ksplit, rms_eps, ssq, tile, s);
+  // workspace: [ksplit][M][N] fp32 partial slabs, then (fused norm) [ksplit][M] partial sums of squares
+  const size_t slabs = (size_t)p.ksplit * M * N;
+  if (ws == nullptr || ws_floats < slabs + (p.norm != NORM_NONE ? (size_t)p.ksplit * M : 0)) return -3;
+  float* ssq = p.norm != NORM_NONE ? ws + slabs : nullptr;
+  launch_plan<MODE_PARTIAL>(GemmArgs{x, w, ws, M, N, K, 0, 1, nullptr, rms_eps, ssq, nullptr, QKVArgs{}, s}, p);
   JLA_CHECK_LAUNCH();
-  return launch_reduce(ws, ksplit, out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ssq, rms_eps, s);
+  return launch_reduce(ws, p.ksplit, out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ssq, rms_eps, s);
 }
 
 // ---- greedy lm_head: GEMM with the argmax in its epilogue (no fp32 logits round trip through HBM:
@@ -1832,27 +1653,17 @@ size_t gemm_argmax_workspace_floats(int M, int N) { return (size_t)M * ((N + G2_
 
 int gemm_argmax(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int M, int N, int K, float rms_eps,
                 int32_t* idx, float* val, hipStream_t s, float* rms_ws, size_t rms_ws_floats) {
-  if (rms_ws != nullptr && rms_ws_floats < (size_t)M) rms_ws = nullptr;
-  if (M <= 0) return 0;
-  if ((N & 15) || (K & 31)) return -1;
+  const bool has_rms_ws = rms_ws != nullptr && rms_ws_floats >= (size_t)M;
+  const GemmPlanResult r = gemm_plan(M, N, K, MODE_ARGMAX, rms_eps >= 0.f, 1, 0, has_rms_ws, 0, 0, g_g4_default);
+  if (r.rc != 0 || r.plan.family == GEMM_NONE) return r.rc;
   if (ws == nullptr || ws_floats < gemm_argmax_workspace_floats(M, N)) return -3;
-  const int tm = (M + 255) / 256, tn = (N + G2_BN - 1) / G2_BN;
-  const u32x4* w = static_cast<const u32x4*>(W);
-  if (use_g4(0, M, K)) {  // 2 partials per 256-column tile (one per wave column)
-    launch_g4<MODE_ARGMAX>(x, w, ws, M, N, K, 0, 1, nullptr, 1, rms_eps, nullptr, s, QKVArgs{}, rms_ws);
-    JLA_CHECK_LAUNCH();
-    launch_argmax_partials(reinterpret_cast<const float2*>(ws), tn * 2, M, idx, val, s);
-    JLA_CHECK_LAUNCH();
-    return 0;
-  }
-  if (rms_eps >= 0.f)
-    gemm2_kernel<MODE_ARGMAX, 2, 4, true, true, 8, 4, 1, true, 2><<<tm * tn, 512, 0, s>>>(
-        x, w, ws, M, N, K, 0, 1, nullptr, K >> 5, tm, tn, rms_eps, nullptr, QKVArgs{});
-  else
-    gemm2_kernel<MODE_ARGMAX, 2, 4, true, false, 8, 4, 1, true, 2><<<tm * tn, 512, 0, s>>>(
-        x, w, ws, M, N, K, 0, 1, nullptr, K >> 5, tm, tn, rms_eps, nullptr, QKVArgs{});
+  launch_plan<MODE_ARGMAX>(
+      GemmArgs{x, static_cast<const u32x4*>(W), ws, M, N, K, 0, 1, nullptr, rms_eps, nullptr, rms_ws, QKVArgs{}, s},
+      r.plan);
   JLA_CHECK_LAUNCH();
-  launch_argmax_partials(reinterpret_cast<const float2*>(ws), tn * 4, M, idx, val, s);
+  // one partial per wave column: 2 per 256-column gemm4 tile, 4 per gemm2 tile
+  const int P = (N + G2_BN - 1) / G2_BN * (r.plan.family == GEMM4 ? 2 : 4);
+  launch_argmax_partials(reinterpret_cast<const float2*>(ws), P, M, idx, val, s);
   JLA_CHECK_LAUNCH();
   return 0;
 }

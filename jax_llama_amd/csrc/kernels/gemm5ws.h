@@ -32,7 +32,6 @@ namespace jla {
 
 constexpr int G5_A = 3;              // K-stages in flight beyond the one being computed
 constexpr int G5_SLOTS = G5_A + 1;   // x stage slots in LDS / weight register ring slots
-constexpr int G5_TILE = 11;          // tile config id (gemm.hip dispatch, ops/autotune.py): NTW 4; 12: NTW 2
 __device__ u32x4 g5_zero_frag[64];   // 1 KiB of zeros: the weight fragment of stages past the end (MFMA adds 0)
 
 template <int MT, int NTW>

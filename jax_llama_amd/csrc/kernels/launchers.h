@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_plan.h"
+
 #define SKINNY_MAX_M 64
 
 namespace jla {
@@ -68,36 +70,31 @@ size_t gemv_split_workspace_floats(int M, int N);
 int gemv_split_tickets(int N);
 inline bool gemv_split_variant(int v) { return v == 16 || v == 18 || v == 26; }
 inline bool gemv_xp_variant(int v) { return v == 12 || v == 15 || v == 18 || v == 21 || v == 22 || v == 26; }
-// 128x128-tile MFMA GEMM (gemm.hip). ksplit > 1 splits K over gridDim.z into fp32 partials
-// (ws >= gemm_workspace_floats) reduced in fixed order by an epilogue kernel; MODE_QKV needs ksplit > 1.
-int gemm_ksplit(int M, int N, int K);
-int gemm_qkv_direct_ok(int M, int tile, int K);  // qkv without a K split: the direct RoPE / KV-write GEMM epilogue applies
-// gemm4 (the 4-wave 256 x 256 kernel, tile config 7) as the tile-0 default for M > 128, K % 64 == 0 (on by default)
-void gemm_set_g4_default(int on);
-void gemm_set_g4_group(int gm);
-int gemm5_ksplit(int K, int ksplit);
 int clock_probe(int iters, int grid, unsigned long long* out, hipStream_t s);  // [cycles, 100 MHz ticks]
-void gemm5_set_diag(int d);  // tools only: gemm5 ablations (wrong results)  // gemm5 (tiles 11 / 12): the effective split over 64-deep K-stages
-size_t gemm_workspace_floats(int M, int N, int K);
-// rms_eps >= 0: x is the UNscaled activation and each output row is scaled by rsqrt(mean(x^2) + eps)
-// (fused RMSNorm; not for MODE_RESIDUAL); split-K then needs ws >= ksplit * M * (N + 1) floats.
-// tile: gemm2 tile config 1 = 256x256, 2 = 128x256, 3 = 128x128, 0 = by M; 7 / 10 gemm4 (256 x 256 / 256 x 128),
-// 8 gemm4 exchange split (above), 11 / 12 gemm5
-// workgroups (= fused-exchange regions and call counters) of gemm()'s MODE_TPRESID reduce at M x N: the row-parallel
-// projection's split-K reduce with the TP all-reduce and residual add in its epilogue (out = h, mirror = hb,
-// qkv->tp = the group's CarDevice; split plans only)
-int gemm_tp_groups(int M, int N);
+// Tiled MFMA GEMM (gemm.hip): y = epilogue(x[M, K] @ W[N, K]^T) on the kernel the tile id names (gemm_plan.h: the
+// tile table, and gemm_plan(), every rule of a legal call; the return codes -1 / -5 / -6 / -7 are its). ksplit > 1
+// splits K over workgroups into fp32 partial slabs (ws >= ksplit * M * N floats, + ksplit * M under the fused norm;
+// gemm5: for any split, gemm5_ksplit(K, ksplit) slabs; -3: too small) that gemm_reduce_kernel sums in fixed order before
+// it runs the epilogue. gemm_ksplit / gemm_workspace_floats: the library's split heuristic and its workspace.
+// rms_eps >= 0: x is the UNscaled activation and each output row is scaled by rsqrt(mean(x^2) + eps) (fused RMSNorm;
+// not for MODE_RESIDUAL). rms_ws (>= M floats): a gemm4 plan without a K split computes the row statistic ahead of the
+// GEMM into it (rms_rowinv) instead of inside its main loop; null: in-loop statistic.
+// n_body (tail-balanced tiles): > 0 pins the body n-tile count, 0 takes gemm_tail_split(m-tiles, N, width, CUs).
+// MODE_TPRESID: the row-parallel projection's split-K reduce with the TP all-reduce and residual add in its epilogue
+// (out = h, mirror = hb, qkv->tp = the group's CarDevice; split plans only).
 int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mode, int accumulate, int out_f32,
          bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit, hipStream_t s,
          float rms_eps = -1.f, int tile = 0, float* rms_ws = nullptr, size_t rms_ws_floats = 0, int n_body = 0);
-// tile configs 18 / 19 (tail-balanced gemm4: body tiles of gemm_tail_width(tile) columns, then 128-wide tail tiles):
-// n_body > 0 pins the body n-tile count, 0 takes gemm_tail_split(m-tiles, N, width, CUs) -- 0 from that: no split beats
-// the uniform grid of that width, and gemm() returns -7
-int gemm_tail_width(int tile);
-int gemm_tail_split(int tiles_m, int N, int width, int cus);
-int gemm_num_cus();  // CUs of the current device
-// rms_ws (>= M floats): with the fused norm, a gemm4 plan without a K split computes the row statistic ahead of
-// the GEMM into it (rms_rowinv) instead of inside its main loop; null: in-loop statistic
+// gemm_plan()'s return code for this call on the current device (MODE_ARGMAX: as gemm_argmax() runs it)
+int gemm_plan_check(int M, int N, int K, int mode, int rms, int ksplit, int tile, int has_rms_ws, int n_body);
+int gemm_ksplit(int M, int N, int K);
+size_t gemm_workspace_floats(int M, int N, int K);
+int gemm_tp_groups(int M, int N);  // workgroups (= fused-exchange regions and call counters) of the MODE_TPRESID reduce
+int gemm_qkv_direct_ok(int M, int tile, int K);  // qkv without a K split: the direct RoPE / KV-write GEMM epilogue applies
+int gemm_num_cus();                // CUs of the current device (gemm_plan's `cus`)
+void gemm_set_g4_default(int on);  // gemm_plan's `g4_default`: tile 0 runs gemm4 where it applies (on by default)
+void gemm_set_g4_group(int gm);    // tools: m-tiles per group of gemm4's launch order (0: the default, 4)
+void gemm5_set_diag(int d);        // tools only: gemm5 / gemm4 store ablations (wrong results)
 // greedy lm_head: GEMM + first-max argmax epilogue (ws >= gemm_argmax_workspace_floats(M, N) floats)
 int gemm_argmax(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int M, int N, int K, float rms_eps,
                 int32_t* idx, float* val, hipStream_t s, float* rms_ws = nullptr, size_t rms_ws_floats = 0);

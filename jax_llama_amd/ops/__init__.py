@@ -302,7 +302,7 @@ def tiled_tp_residual(x: torch.Tensor, w, h: torch.Tensor, hb: torch.Tensor, sta
     m = x.shape[0]
     assert x.dtype == BF16 and x.is_contiguous(), (x.dtype, x.shape)
     ks, tm = autotune.choose_gemm_plan(e, m, w.n, w.k, x.device, MODE_STORE, False)
-    if tm not in G5_TILES and ks <= 1:
+    if tm not in autotune.G5_TILES and ks <= 1:
         return False
     ks, tm, ws = _gemm_ws(e, m, w.n, w.k, x.device, MODE_STORE, False)
     e.gemm_tp_residual(state, x, w.weight, w.n, w.k, h, hb, ks, ws, tm)
@@ -329,14 +329,11 @@ def _tiled_input(x, rms_eps, fused=False):
     return x if x.dtype == BF16 else x.to(BF16)
 
 
-G5_TILES = (11, 12)  # gemm5 weight-streaming split-K (csrc/kernels/gemm5ws.h): 256- / 128-column workgroups
-
-
 def _gemm_ws(e, m, n, k, device, mode=MODE_STORE, rms=False):
     """(split-K factor, tile config, workspace) of the tuned plan for this shape and epilogue: the partial slabs of a
     split summed by the reduce kernel (gemm5, tiles 11 / 12: always)."""
     ks, tm = autotune.choose_gemm_plan(e, m, n, k, device, mode, rms)
-    if tm in G5_TILES:  # weight-streaming split-K (any split, slabs always): partial slabs + the reduce kernel
+    if tm in autotune.G5_TILES:  # weight-streaming split-K (any split, slabs always): partial slabs + the reduce kernel
         eks = e.gemm5_ksplit(k, ks)
         return ks, tm, workspace.get("gemm_ws", eks * m * (n + 1), torch.float32, device)
     # split-K slabs [ks][m][n] + the fused-RMS partial sums of squares [ks][m]
@@ -369,7 +366,7 @@ def _tiled_packs(e, m, n, k, device, mode, rms_eps) -> bool:
     if e is None or m > SKINNY_M or mode not in (MODE_RESIDUAL, MODE_SWIGLU):
         return False
     ks, tm = autotune.choose_gemm_plan(e, m, n, k, device, mode, _fused_rms(e, mode, rms_eps))
-    if tm in G5_TILES:
+    if tm in autotune.G5_TILES:
         return True
     return ks > 1
 

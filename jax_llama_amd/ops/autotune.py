@@ -29,7 +29,7 @@ from __future__ import annotations
 import contextlib
 import json
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
@@ -298,13 +298,9 @@ def measured() -> Dict[Tuple, Dict[int, float]]:
 # (profiles/README.md). Timed once per shape when the library heuristic asks for a split.
 _KS_CACHE: Dict[Tuple, Tuple[int, int]] = {}
 KS_CANDIDATES = (1, 2, 3, 4, 6, 8, 12, 16)
-# tile configs: 1 / 2 / 3 gemm2 256x256, 128x256, 128x128 (csrc/kernels/gemm.hip tile_cfg); 7 gemm4; 14 gemm4 with the
-# weights three K-tiles deep (160 KiB of LDS); 17 / 16 gemm4 on 256 x 128 / 192 tiles with the deep weights (no K split
-# under the fused norm, its statistic is precomputed); 18 / 19 tail-balanced gemm4: a body of 256 x 192 / 256 tiles in
-# whole rounds of the CUs, then the remaining columns as 256 x 128 tiles (gemm.hip gemm4t_kernel; same guards as 16 / 17,
-# never split, offered only where gemm_tail_split finds a split that beats the uniform grid); 11 / 12: gemm5, the
-# weight-streaming split-K kernel (gemm5ws.h; 256 / 128 columns per workgroup, M <= 256 per tile). What the bench shapes
-# pick (BENCH_r05 gemm_plan_choice; gate_up at M = 2048: profiles/gemm4t_kernel_ab.jsonl):
+# tile configs the tuner offers (the table of ids and every rule of a legal plan: csrc/kernels/gemm_plan.h, asked
+# through gemm_plan_check). What the bench shapes pick (BENCH_r05 gemm_plan_choice; gate_up at M = 2048:
+# profiles/gemm4t_kernel_ab.jsonl):
 #   Llama-3-8B M = 1024 / 2048: qkv 16 / 17, o 17, gate_up 7 / 14 / 19, down 14 / 17 (split 2), lm_head 14;
 #   Llama-3-70B M = 256 (MP 1 and the MP 8 shard): 1 / 3 (split 4 / 12), 11 / 12 (gemm5 splits), 14, 17.
 TILE_CANDIDATES = (1, 2, 3, 7, 11, 12, 14, 16, 17, 18, 19)
@@ -343,13 +339,7 @@ def choose_gemm_plan(e, m: int, n: int, k: int, device, mode: int = 0, rms: bool
     return plan
 
 
-def choose_gemm_ksplit(e, m: int, n: int, k: int, device) -> int:
-    return choose_gemm_plan(e, m, n, k, device)[0]
-
-
-G4N_TILES = (16, 17)  # gemm4 on 256 x 192 / 128 tiles (csrc/kernels/gemm4w.h g4n_mainloop, deep weights)
-G4T_TILES = {18: 192, 19: 256}  # tail-balanced gemm4: body tile width (the tail tiles are 128 wide; gemm.hip gemm4t_kernel)
-G5_TILES = (11, 12)  # gemm5 weight-streaming split-K (csrc/kernels/gemm5ws.h)
+G5_TILES = (11, 12)  # gemm5, the weight-streaming split-K kernel: slabs and the reduce kernel for any split
 TUNE_ROUNDS = 3
 
 
@@ -358,20 +348,30 @@ TUNE_ROUNDS = 3
 TUNE_WS_BYTES = int(float(os.environ.get("JLA_TUNE_WS_GB", "4")) * (1 << 30))
 
 
-def _measure_plan(e, m, n, k, device, heur, mode=0, rms=False) -> Tuple[int, int]:
+def plan_candidates(e, m, n, k, mode=0, rms=False, heur=None) -> List[Tuple[int, int]]:
+    """The (split-K factor, tile config) plans ``_measure_plan`` times for this shape and epilogue, in measuring order
+    (the order decides ties). Tuning policy picks the pairs: every tile candidate x every split that keeps >= 4 K-tiles
+    per split and fits the scratch budget (plus the library heuristic's split), gemm5 only for M <= 512 but also at the
+    deeper splits its 64-deep stages allow. Legality is not restated here: ``gemm_plan_check`` (csrc/kernels/gemm_plan.h)
+    is asked about each pair as ``_measure_plan`` runs it, the norm scratch present where there is no split."""
     kt = k // 32
+    heur = e.gemm_ksplit(m, n, k) if heur is None else heur
+    rms = bool(rms) and mode != 1
 
     def fits(c):
         return c * m * (n + 1) * 4 <= TUNE_WS_BYTES
 
     ks_c = sorted({c for c in KS_CANDIDATES if kt // c >= 4 and fits(c)} | ({heur} if fits(heur) else set()) | {1})
+    # (policy: where K % 64 != 0 the id 16 is legal but runs gemm2 by M, a plan already measured under ids 1 / 2)
     cands = [(c, tm) for tm in TILE_CANDIDATES for c in ks_c
-             if (tm not in G4N_TILES or (k % 64 == 0 and not (c > 1 and rms and mode != 1)))
-             and (tm not in G4T_TILES or (k % 64 == 0 and c == 1
-                                          and e.gemm_tail_split((m + 255) // 256, n, G4T_TILES[tm])[0] > 0))
-             and (tm not in G5_TILES or (k % 64 == 0 and m <= 512))]
-    if k % 64 == 0 and m <= 512:  # gemm5 also at the deeper splits its 64-deep stages allow (narrow shards, long K)
+             if (tm not in G5_TILES or m <= 512) and not (tm == 16 and k % 64)]
+    if m <= 512:
         cands += [(c, tm) for tm in G5_TILES for c in (24, 32, 48) if (k // 64) // c >= 2 and c not in ks_c and fits(c)]
+    return [(c, tm) for c, tm in cands if e.gemm_plan_check(m, n, k, mode, rms, c, tm, c == 1 and rms) == 0]
+
+
+def _measure_plan(e, m, n, k, device, heur, mode=0, rms=False) -> Tuple[int, int]:
+    cands = plan_candidates(e, m, n, k, mode, rms, heur)
     nbytes = n * k * 2
     copies = max(2, min(16, (640 << 20) // max(nbytes, 1) + 1))
     ws_w = [torch.empty(n // 16, k // 32, 64, 8, dtype=torch.bfloat16, device=device).normal_(0, 0.02)

@@ -102,21 +102,21 @@ def main():
                   e.gemm_set_g4_group(grp)
                   for tile in args.tile:
                     kk = ks or e.gemm_ksplit(m, n, k)
-                    if tile in (16, 17) and kk > 1 and eps > 0:
-                        continue  # (gemm4 256 x 128 / 192: no K split under the fused norm)
-                    if tile in (18, 19) and (kk > 1 or e.gemm_tail_split((m + 255) // 256, n, 192 if tile == 18 else 256)[0] == 0):
-                        continue  # (tail-balanced gemm4: no K split; only where a split beats the uniform grid)
-                    if kk > 1 and (k // 32) // kk < 4 and tile not in (11, 12):
+                    g5 = tile in ops.autotune.G5_TILES
+                    if kk > 1 and (k // 32) // kk < 4 and not g5:
                         continue
-                    if tile in (11, 12) and (k % 64 or (k // 64) // kk < 1):
+                    if g5 and (k // 64) // kk < 1:
                         continue
+                    has_rws = eps > 0 and kk == 1 and not g5
+                    if e.gemm_plan_check(m, n, k, mode, eps > 0, kk, tile, has_rws) != 0:
+                        continue  # (no legal plan: csrc/kernels/gemm_plan.h)
                     ws = torch.empty(max(1, kk * m * (n + 1)), device=DEV, dtype=torch.float32)
                     tcfg = tile
-                    rws = torch.empty(m, device=DEV) if (eps > 0 and kk == 1 and tile not in (11, 12)) else None
+                    rws = torch.empty(m, device=DEV) if has_rws else None
 
                     def run(i, kk=kk, ws=ws, tile=tcfg, rws=rws):
                         e.gemm(x, packed[i % copies].weight, n, k, out, mode, True, mir if mode == 1 else None, kk,
-                               ws if (kk > 1 or tile in (11, 12)) else None, eps, tile, None, rws)
+                               ws if (kk > 1 or tile in ops.autotune.G5_TILES) else None, eps, tile, None, rws)
                     res[f"v{impl}_ks{kk}_t{tile}" + (f"_diag{diag}" if diag else "") + (f"_g{grp}" if grp else "")  + "" +
                         (f"_r{rnd}" if args.rounds > 1 else "")] = timeit(run, iters)
                     run(0)
