@@ -165,12 +165,17 @@ def test_attention_decode_streaming_v2(rep, t, slot, masked):
         mask[:, slot] = 1
     expect = ref.attention(q, kc, vc, slot, kv_start, mask).reshape(b, h * dh)
     try:
-        e.attn_set_impl(2, -1)  # v2 for any batch size
+        e.attn_set_impl(2, -1)  # v2 for any batch size ...
+        e.attn_set_v5_max_pairs(0)  # ... once the small-batch kernels the dispatcher asks first (v5, then v3) are off
+        e.attn_set_v3_max_pairs(0)
+        assert not e.attn_decode_packs(b, hkv, rep)  # (v6 / v5 / v3 would write the packed copy)
         got = ops.attention(q.to(DEV), kc.to(DEV), vc.to(DEV), torch.tensor([slot], dtype=torch.int32, device=DEV),
                             kv_start.to(DEV), None if mask is None else mask.to(DEV))
         torch.cuda.synchronize()
     finally:
         e.attn_set_impl(2, 0)
+        e.attn_set_v5_max_pairs(-1)
+        e.attn_set_v3_max_pairs(4096)
     _close(got, expect, 2e-2, 2e-2)
     assert got[2].float().abs().max().item() == 0.0
 
