@@ -7,7 +7,7 @@ Multi-GPU: one process per GPU, RCCL + a custom xGMI all-reduce. Decode: hipGrap
 from .config import LLaMAConfig, ModelArgs, config_from_params, get_preset, swiglu_hidden_size
 from .generation import LLaMA
 from .models import (CausalLMOutput, FlaxLLaMAForCausalLM, FlaxLLaMAModel, KVCache, LLaMAForCausalLM,
-                     LLaMAModel)
+                     LLaMAModel, ScoreOutput)
 from .parallel.partition import (Mesh, P, PartitionSpec, get_llama_param_partition_spec,
                                  with_named_sharding_constraint, with_sharding_constraint)
 from .runtime.engine import GenerationConfig
@@ -19,7 +19,7 @@ __version__ = "0.1.0"
 __all__ = [
     "LLaMAConfig", "ModelArgs", "config_from_params", "get_preset", "swiglu_hidden_size",
     "LLaMA", "LLaMAForCausalLM", "LLaMAModel", "FlaxLLaMAForCausalLM", "FlaxLLaMAModel",
-    "CausalLMOutput", "KVCache", "GenerationConfig",
+    "CausalLMOutput", "ScoreOutput", "KVCache", "GenerationConfig",
     "Mesh", "P", "PartitionSpec", "get_llama_param_partition_spec", "with_named_sharding_constraint",
     "with_sharding_constraint", "LLaMA2Tokenizer", "LLaMA3Tokenizer", "ChatFormat", "convert_llama_weights",
 ]

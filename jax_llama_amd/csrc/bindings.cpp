@@ -552,6 +552,48 @@ void gemm_argmax(Tensor x, Tensor w, int64_t n, int64_t k, Tensor ws, double rms
      "gemm_argmax");
 }
 
+static void check_logprob_io(const Tensor& targets, const Tensor& tgt, const Tensor& mx, const Tensor& se, int64_t m,
+                             int64_t col_offset) {
+  for (auto* t : {&targets, &tgt, &mx, &se}) check_gpu(*t, "logprob arg");
+  check(targets.scalar_type() == torch::kInt32 && targets.numel() == m, "targets must be int32 [M]");
+  for (auto* t : {&tgt, &mx, &se})
+    check(t->scalar_type() == torch::kFloat32 && t->numel() == m, "logprob outputs must be fp32 [M]");
+  check(col_offset >= 0 && col_offset <= INT32_MAX, "col_offset");
+}
+
+// Scoring lm_head: tiled GEMM (fused RMS when rms_eps >= 0) with the log-sum-exp in its epilogue; the fp32 logits are
+// never written. Per row of this weight shard: tgt = the logit at column targets - col_offset (0 outside [0, n)), mx =
+// the row maximum, se = sum exp(logit - mx). ws: fp32 >= gemm_logprob_workspace(m, n) floats.
+void gemm_logprob(Tensor x, Tensor w, int64_t n, int64_t k, Tensor ws, double rms_eps, Tensor targets,
+                  int64_t col_offset, Tensor tgt, Tensor mx, Tensor se, c10::optional<Tensor> rms_ws) {
+  check_gpu(x, "x");
+  check_packed(w, n, k);
+  check(x.dim() == 2 && x.size(1) == k && x.scalar_type() == torch::kBFloat16, "x must be bf16 [M, K]");
+  const int64_t m = x.size(0);
+  check_gpu(ws, "ws");
+  check(ws.scalar_type() == torch::kFloat32 && (size_t)ws.numel() >= jla::gemm_logprob_workspace_floats(m, n),
+        "gemm_logprob ws too small");
+  check_logprob_io(targets, tgt, mx, se, m, col_offset);
+  size_t rfl = 0;
+  float* rws = rms_ws_ptr(rms_ws, m, &rfl);
+  gemm_rc(jla::gemm_logprob(cbf(x), w.data_ptr(), ptr<float>(ws), ws.numel(), m, n, k, (float)rms_eps,
+                            ptr<int32_t>(targets), (int)col_offset, ptr<float>(tgt), ptr<float>(mx), ptr<float>(se),
+                            stream(), rws, rfl),
+          "gemm_logprob");
+}
+
+// the same triple from stored fp32 logits [B, V]
+void logprob_rows(Tensor logits, Tensor targets, int64_t col_offset, Tensor tgt, Tensor mx, Tensor se) {
+  check_gpu(logits, "logits");
+  check(logits.scalar_type() == torch::kFloat32 && logits.dim() == 2 && logits.size(1) > 0,
+        "logits must be fp32 [B, V]");
+  check(logits.size(1) <= INT32_MAX, "logprob_rows: V too large");
+  check_logprob_io(targets, tgt, mx, se, logits.size(0), col_offset);
+  rc(jla::logprob_rows(ptr<float>(logits), logits.size(0), logits.size(1), ptr<int32_t>(targets), (int)col_offset,
+                       ptr<float>(tgt), ptr<float>(mx), ptr<float>(se), stream()),
+     "logprob_rows");
+}
+
 // stage 1 of the sampler: per-4096-chunk top-K candidates (global indices = local + idx_offset)
 void topk_chunk(Tensor logits, int64_t k, int64_t idx_offset, Tensor cv, Tensor ci) {
   for (auto* t : {&logits, &cv, &ci}) check_gpu(*t, "topk_chunk arg");
@@ -808,6 +850,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("gemm_argmax", &gemm_argmax, py::arg("x"), py::arg("w"), py::arg("n"), py::arg("k"), py::arg("ws"),
         py::arg("rms_eps"), py::arg("idx"), py::arg("val"), py::arg("rms_ws") = py::none());
   m.def("gemm_argmax_workspace", [](int64_t m, int64_t n) { return (int64_t)jla::gemm_argmax_workspace_floats(m, n); });
+  m.def("gemm_logprob", &gemm_logprob, py::arg("x"), py::arg("w"), py::arg("n"), py::arg("k"), py::arg("ws"),
+        py::arg("rms_eps"), py::arg("targets"), py::arg("col_offset"), py::arg("tgt"), py::arg("mx"), py::arg("se"),
+        py::arg("rms_ws") = py::none());
+  m.def("gemm_logprob_workspace",
+        [](int64_t m, int64_t n) { return (int64_t)jla::gemm_logprob_workspace_floats(m, n); });
+  m.def("logprob_rows", &logprob_rows);
   m.def("gemm_ksplit", [](int64_t m, int64_t n, int64_t k) { return jla::gemm_ksplit(m, n, k); });
   m.def("rope_kv_write", &rope_kv_write);
   m.def("attn_set_impl", [](int64_t impl, int64_t waves_target) { jla::attn_set_impl(impl, waves_target); },

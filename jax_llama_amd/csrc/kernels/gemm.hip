@@ -673,8 +673,8 @@ template <int MODE, int RMSM, typename Acc, int NJ = 8>
 JLA_DEV void g4_epilogue(Acc& acc, float* ss, u32x4* lds, int wu, int lane, int m0, int n0, int split,
                          const G4Epi& ep, const QKVArgs& qa) {
   constexpr bool RMS = RMSM == 1;
-  static_assert(NJ == 8 || (RMSM != 1 && MODE != MODE_ARGMAX),
-                "the 256 x 128 / 192 tiles: precomputed norm statistic; no argmax epilogue");
+  static_assert(NJ == 8 || (RMSM != 1 && MODE != MODE_ARGMAX && MODE != MODE_LOGPROB),
+                "the 256 x 128 / 192 tiles: precomputed norm statistic; no argmax / log-prob epilogue");
   constexpr int WN = 16 * NJ;  // output columns of a wave block
   constexpr int PJ = NJ == 6 ? 8 : NJ;  // staged row width in n-tiles (a power of two; NJ = 6 leaves the rest unused)
   const int wr = wu >> 1, wc = wu & 1;
@@ -787,6 +787,60 @@ JLA_DEV void g4_epilogue(Acc& acc, float* ss, u32x4* lds, int wu, int lane, int 
       }
       const int row = rbase + 16 * i;
       if (q == 0 && row < M) o[(size_t)row * P + slot] = make_float2(bv, __int_as_float(bi));
+    }
+  } else if constexpr (MODE == MODE_LOGPROB) {
+    // per row over this wave's 128 columns: m = the maximum and s = sum exp(v - m) of the valid ones -> one (m, s)
+    // partial at [row][n0 / 128 + wc] (the argmax partials' layout; lse_partials_kernel finishes the row), and the
+    // logit at the row's target column, stored by the one lane of the grid that holds it. A wave block with no valid
+    // column writes (-inf, 0), the identity of every merge. Two passes over the accumulators (the maximum, then the
+    // sum against it), in a fixed order and without atomics: the same bits on every call.
+    float2* o = static_cast<float2*>(out);
+    const int P = tiles_n * 2, slot = (n0 >> 7) + wc, tile0 = (n0 >> 4) + wc * 8;
+    const int32_t* const targets = qa.lp_targets;
+    float* const tgt = qa.lp_tgt;
+    const int col_offset = qa.lp_col_offset;
+    // the targets of this lane's 8 rows, loaded as one batch -> the n-tile of this wave block (0..7) in which this
+    // lane holds the target column, or -1 (another lane's, another wave's, an ignored label, another rank's shard)
+    int tg[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) tg[i] = targets[min(rbase + 16 * i, M - 1)];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int col = tg[i] - col_offset;
+      const bool mine = col >= 0 && col < N && ((col >> 2) & 3) == q && (unsigned)((col >> 4) - tile0) < 8u;
+      tg[i] = mine ? (((col >> 4) - tile0) << 2 | (col & 3)) : -1;
+    }
+    constexpr float LOG2E = 1.4426950408889634f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float m = -INFINITY, tv_t = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f32x4 tv = tile_val(j, i);
+        if (tile0 + j < NTT) m = fmaxf(fmaxf(m, fmaxf(tv[0], tv[1])), fmaxf(tv[2], tv[3]));
+        if ((tg[i] >> 2) == j) {  // (-1 >> 2 = -1: never)
+          const int r = tg[i] & 3;
+          tv_t = r == 0 ? tv[0] : (r == 1 ? tv[1] : (r == 2 ? tv[2] : tv[3]));
+        }
+      }
+      m = fmaxf(m, __shfl_xor(m, 16, 64));
+      m = fmaxf(m, __shfl_xor(m, 32, 64));
+      float s = 0.f;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const f32x4 tv = tile_val(j, i);
+        if (tile0 + j < NTT) {  // (a valid column makes m finite: no inf - inf)
+#pragma unroll
+          for (int r = 0; r < 4; ++r) s += __builtin_amdgcn_exp2f((tv[r] - m) * LOG2E);
+        }
+      }
+      s += __shfl_xor(s, 16, 64);
+      s += __shfl_xor(s, 32, 64);
+      const int row = rbase + 16 * i;
+      if (row < M) {
+        if (q == 0) o[(size_t)row * P + slot] = make_float2(m, s);
+        if (tg[i] >= 0) tgt[row] = tv_t;
+      }
     }
   } else if constexpr (MODE == MODE_QKV) {
     // RoPE on the two (even, odd) pairs of the lane's 4 columns in fp32, then staged: 16-byte pieces of a row go to
@@ -1473,10 +1527,12 @@ static void launch_plan(const GemmArgs& a, const GemmPlan& p) {
   switch (p.family) {
     case GEMM2_256x256:
     case GEMM2_128x256:
-    case GEMM2_128x128: launch_g2<MODE>(a, p); break;
+    case GEMM2_128x128:
+      if constexpr (MODE != MODE_LOGPROB) launch_g2<MODE>(a, p);  // (gemm2 has no log-prob epilogue)
+      break;
     case GEMM4:
       if (p.nj == 8) launch_g4<MODE, 8>(a, p);
-      if constexpr (MODE != MODE_ARGMAX) {
+      if constexpr (MODE != MODE_ARGMAX && MODE != MODE_LOGPROB) {
         if (p.nj == 6) launch_g4<MODE, 6>(a, p);
       }
       if constexpr (PLAIN || MODE == MODE_PARTIAL) {
@@ -1546,7 +1602,8 @@ int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mod
       gemm_plan(M, N, K, mode, rms_eps >= 0.f, ksplit, tile, has_rms_ws, n_body, num_cus(), g_g4_default);
   const GemmPlan& p = r.plan;
   if (r.rc != 0 || p.family == GEMM_NONE) return r.rc;
-  if (mode == MODE_ARGMAX || (mode == MODE_QKV && !qkv)) return -1;  // (gemm_argmax()'s epilogue)
+  // (gemm_argmax()'s and gemm_logprob()'s epilogues)
+  if (mode == MODE_ARGMAX || mode == MODE_LOGPROB || (mode == MODE_QKV && !qkv)) return -1;
   const u32x4* w = static_cast<const u32x4*>(W);
   if (!p.reduce) {  // the epilogue in the tile kernel
     GemmArgs a{x, w, out, M, N, K, accumulate, out_f32, nullptr, rms_eps, nullptr, rms_ws, QKVArgs{}, s};
@@ -1664,6 +1721,100 @@ int gemm_argmax(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int
   // one partial per wave column: 2 per 256-column gemm4 tile, 4 per gemm2 tile
   const int P = (N + G2_BN - 1) / G2_BN * (r.plan.family == GEMM4 ? 2 : 4);
   launch_argmax_partials(reinterpret_cast<const float2*>(ws), P, M, idx, val, s);
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- scoring lm_head: GEMM with the log-sum-exp in its epilogue (MODE_LOGPROB in g4_epilogue: no fp32 logits round
+// trip through HBM, 16.8 GB written + read at M = 32768, V = 128256), then the [M][P] (max, sum) partials are merged
+// per row. (m, s) stands for s * exp(m); (-inf, 0) is the identity and never meets an inf - inf.
+JLA_DEV void lse_merge(float& m, float& s, float om, float os) {
+  constexpr float LOG2E = 1.4426950408889634f;
+  if (om == -INFINITY) return;
+  if (m == -INFINITY) {
+    m = om;
+    s = os;
+    return;
+  }
+  const float nm = fmaxf(m, om);
+  s = s * __builtin_amdgcn_exp2f((m - nm) * LOG2E) + os * __builtin_amdgcn_exp2f((om - nm) * LOG2E);
+  m = nm;
+}
+
+// The launch shapes of argmax_partials_kernel (TPR threads per row, 4 independent partials in flight per thread). The
+// merge order is fixed by (P, TPR): per thread its strided partials in order, then the 4 candidates, the lanes of a
+// wave by xor 32..1, the waves in order -- the same bits on every call.
+template <int TPR>
+__global__ void __launch_bounds__(TPR == 64 ? 256 : TPR)
+    lse_partials_kernel(const float2* __restrict__ part, int P, int M, float* __restrict__ mx,
+                        float* __restrict__ se) {
+  __shared__ float s_m[16];
+  __shared__ float s_s[16];
+  const int row = TPR == 64 ? blockIdx.x * 4 + (threadIdx.x >> 6) : blockIdx.x;
+  const int t = TPR == 64 ? (threadIdx.x & 63) : threadIdx.x;
+  if (row >= M) return;
+  const float2* pr = part + (size_t)row * P;
+  float bm[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  float bs[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int k0 = t; k0 < P; k0 += 4 * TPR) {
+    float2 e[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const int k = k0 + u * TPR;
+      e[u] = k < P ? pr[k] : make_float2(-INFINITY, 0.f);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) lse_merge(bm[u], bs[u], e[u].x, e[u].y);
+  }
+#pragma unroll
+  for (int u = 1; u < 4; ++u) lse_merge(bm[0], bs[0], bm[u], bs[u]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1)  // (lane 0's chain is the row's result)
+    lse_merge(bm[0], bs[0], __shfl_xor(bm[0], o, 64), __shfl_xor(bs[0], o, 64));
+  if constexpr (TPR > 64) {
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+      s_m[w] = bm[0];
+      s_s[w] = bs[0];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      for (int ww = 1; ww < TPR / 64; ++ww) lse_merge(bm[0], bs[0], s_m[ww], s_s[ww]);
+      mx[row] = bm[0];
+      se[row] = bs[0];
+    }
+  } else if (t == 0) {
+    mx[row] = bm[0];
+    se[row] = bs[0];
+  }
+}
+
+static void launch_lse_partials(const float2* part, int P, int M, float* mx, float* se, hipStream_t s) {
+  if (M <= 512)
+    lse_partials_kernel<1024><<<M, 1024, 0, s>>>(part, P, M, mx, se);
+  else
+    lse_partials_kernel<64><<<(M + 3) / 4, 256, 0, s>>>(part, P, M, mx, se);
+}
+
+// one (max, sum) pair per wave column of the 256 x 256 gemm4 tile
+size_t gemm_logprob_workspace_floats(int M, int N) { return (size_t)M * ((N + G4_BN - 1) / G4_BN) * 2 * 2; }
+
+int gemm_logprob(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int M, int N, int K, float rms_eps,
+                 const int32_t* targets, int col_offset, float* tgt, float* mx, float* se, hipStream_t s,
+                 float* rms_ws, size_t rms_ws_floats) {
+  const bool has_rms_ws = rms_ws != nullptr && rms_ws_floats >= (size_t)M;
+  const GemmPlanResult r = gemm_plan(M, N, K, MODE_LOGPROB, rms_eps >= 0.f, 1, 0, has_rms_ws, 0, 0, g_g4_default);
+  if (r.rc != 0 || r.plan.family == GEMM_NONE) return r.rc;
+  if (ws == nullptr || ws_floats < gemm_logprob_workspace_floats(M, N)) return -3;
+  if (targets == nullptr || tgt == nullptr || mx == nullptr || se == nullptr) return -1;
+  // rows whose target is an ignored label or a column of another shard are written by nobody
+  const hipError_t zeroed = hipMemsetAsync(tgt, 0, (size_t)M * sizeof(float), s);
+  if (zeroed != hipSuccess) return (int)zeroed;
+  GemmArgs a{x, static_cast<const u32x4*>(W), ws, M, N, K, 0, 1, nullptr, rms_eps, nullptr, rms_ws, QKVArgs{}, s};
+  a.qa.lp_targets = targets, a.qa.lp_tgt = tgt, a.qa.lp_col_offset = col_offset;
+  launch_plan<MODE_LOGPROB>(a, r.plan);
+  JLA_CHECK_LAUNCH();
+  launch_lse_partials(reinterpret_cast<const float2*>(ws), (N + G4_BN - 1) / G4_BN * 2, M, mx, se, s);
   JLA_CHECK_LAUNCH();
   return 0;
 }

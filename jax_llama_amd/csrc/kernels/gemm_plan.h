@@ -11,6 +11,7 @@
 #define MODE_PARTIAL 7  // launch mode of a K split (not a caller's mode): fp32 partial tile to the workspace
 #define MODE_ARGMAX 8   // gemm_argmax() only
 #define MODE_TPRESID 9  // row-parallel partial -> granule all-reduce over the TP group -> residual (gemv.hip)
+#define MODE_LOGPROB 10 // gemm_logprob() only: per-row (max, sum of exponentials) partials + the logit at a target column
 
 namespace jla {
 
@@ -109,7 +110,8 @@ inline GemmPlanResult gemm_plan(int M, int N, int K, int mode, bool rms, int ksp
 
   // ---- gemm5: partial slabs for any split, every epilogue in the reduce kernel
   if (tile == G5_TILE || tile == G5N_TILE) {
-    if (mode == MODE_ARGMAX || (rms && (mode == MODE_RESIDUAL || mode == MODE_TPRESID))) return fail(-1);
+    if (mode == MODE_ARGMAX || mode == MODE_LOGPROB || (rms && (mode == MODE_RESIDUAL || mode == MODE_TPRESID)))
+      return fail(-1);
     if (K <= 0 || !k64 || (N & 15) || M <= 0) return fail(-1);
     if (mode == MODE_SWIGLU && (N & 31)) return fail(-1);
     if (!caller_mode) return fail(-1);
@@ -125,8 +127,9 @@ inline GemmPlanResult gemm_plan(int M, int N, int K, int mode, bool rms, int ksp
   // ---- shape and mode rules of every other tile, in this order
   // (the 256 x 128 tile's combination check comes before the empty batch: illegal is -1 even at M = 0; it sees the
   // requested split, not the effective one)
-  if (tile == G4ND_TILE && (!k64 || (mode == MODE_QKV && ksplit <= 1) || mode == MODE_ARGMAX ||
-                            (rms && mode != MODE_RESIDUAL && (ksplit > 1 || !has_rms_ws))))
+  if (tile == G4ND_TILE &&
+      (!k64 || (mode == MODE_QKV && ksplit <= 1) || mode == MODE_ARGMAX || mode == MODE_LOGPROB ||
+       (rms && mode != MODE_RESIDUAL && (ksplit > 1 || !has_rms_ws))))
     return fail(-1);
   if (M <= 0) return {0, p};
   if (K <= 0 || (N & 15) || (K & 31)) return fail(-1);
@@ -147,14 +150,14 @@ inline GemmPlanResult gemm_plan(int M, int N, int K, int mode, bool rms, int ksp
     p.nj = tile == G4T6_TILE ? 6 : 8;
   } else if (tile == G4ND_TILE) {
     p.family = GEMM4, p.nj = 4, p.deep = true;
-  } else if (tile == G4N6D_TILE && k64 && lmode != MODE_ARGMAX) {
+  } else if (tile == G4N6D_TILE && k64 && lmode != MODE_ARGMAX && lmode != MODE_LOGPROB) {
     p.family = GEMM4, p.nj = 6, p.deep = true;
   } else if (k64 && (tile == G4_TILE || tile == G4P_TILE || tile == G4D_TILE || (tile == 0 && g4_default && M > 128))) {
     // persistent: asked for (13), or the residual epilogue at prefill sizes (o / down at M = 32768 3.5 / 2.4 % faster:
     // the CUs' fp32 read-modify-write bursts desynchronise; the store / SwiGLU / QKV epilogues lose 1.5-3.6 % that
-    // way, profiles/r5_gemm4_persistent_ab.jsonl); never under a K split or with the argmax epilogue
+    // way, profiles/r5_gemm4_persistent_ab.jsonl); never under a K split or with the argmax / log-prob epilogues
     const bool persist = tile == G4P_TILE || (lmode == MODE_RESIDUAL && tile == 0 && M >= 4096);
-    p.family = persist && !split && lmode != MODE_ARGMAX ? GEMM4_PERSISTENT : GEMM4;
+    p.family = persist && !split && lmode != MODE_ARGMAX && lmode != MODE_LOGPROB ? GEMM4_PERSISTENT : GEMM4;
     p.nj = 8, p.deep = tile == G4D_TILE;
   } else if (mode == MODE_ARGMAX) {  // gemm2 has the argmax epilogue on the 256 x 256 tile only
     p.family = GEMM2_256x256;
@@ -182,7 +185,9 @@ inline GemmPlanResult gemm_plan(int M, int N, int K, int mode, bool rms, int ksp
     p.n_body = n_body > 0 ? n_body : gemm_tail_split((M + 255) / 256, N, wb, cus);
     if (p.n_body <= 0 || (long long)p.n_body * wb >= N) return fail(-7);  // no split beats the uniform grid
   }
-  if (mode == MODE_ARGMAX ? split : !caller_mode) return fail(-1);
+  if (mode == MODE_ARGMAX || mode == MODE_LOGPROB ? split : !caller_mode) return fail(-1);
+  // the log-prob epilogue exists on gemm4's 256 x 256 tile only (so K % 64 == 0; gemm2 has none)
+  if (mode == MODE_LOGPROB && !(p.family == GEMM4 && p.nj == 8)) return fail(-1);
 
   // ---- the fused norm: gemm4 without a split reads the precomputed statistic where the scratch is there (the narrow
   // and tail-balanced tiles: always, see above); every other plan sums it in the main loop

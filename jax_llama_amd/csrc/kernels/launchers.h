@@ -26,7 +26,10 @@ int rmsnorm(const float* x, const float* w, float* out, int M, int D, float eps,
 struct QKVArgs {
   const float2* table;        // [table_len, Dh/2] (cos, sin)
   int table_len;
-  const int32_t* positions;   // [M]
+  union {
+    const int32_t* positions;   // [M]
+    const int32_t* lp_targets;  // MODE_LOGPROB: [M] global target columns (outside this shard / negative: ignored)
+  };
   bf16_t* kc;                 // [B, Hkv, T, Dh] (this layer)
   bf16_t* vc;
   const int32_t* slot;        // device int32[1]: cache slot of sequence position 0
@@ -36,10 +39,19 @@ struct QKVArgs {
   bf16_t* pack;               // optional packed-layout copy (common.h pack_off) of the bf16 output: RESIDUAL -> the
                               // mirror, SWIGLU -> the activation (GEMV only; the next projection's packed-x input)
   const void* tp;             // MODE_TPRESID: the TP group's CarDevice (car.h) the partials are all-reduced through
-  float* sk_ws;               // split-K GEMV variants (gemv.hip, 16 / 18 / 26): per-(group, split) partial slabs
+  union {
+    float* sk_ws;             // split-K GEMV variants (gemv.hip, 16 / 18 / 26): per-(group, split) partial slabs
+    float* lp_tgt;            // MODE_LOGPROB: [M] the logit at the target column (zeroed by the launcher; written by the
+  };                          //   one lane that holds it)
   int32_t* sk_tk;             //   and per-group tickets (zero-initialised once, reset by each group's last arriver)
-  int sk_ws_floats;           //   slab buffer size (buffer-descriptor range)
+  union {
+    int sk_ws_floats;         //   slab buffer size (buffer-descriptor range)
+    int lp_col_offset;        // MODE_LOGPROB: global column of this weight shard's column 0 (vocab-parallel TP)
+  };
 };
+// The lp_* names of MODE_LOGPROB (gemm_logprob: no RoPE, no split) share the storage of fields that mode never uses: a
+// larger struct changes the kernel-argument block, and with it the register allocation, of every kernel that takes one.
+
 // MODE_TPRESID: granule bytes each workgroup of the fused row-parallel GEMV owns in every (parity, source rank) slot
 constexpr int CAR_WG_COUNTERS = 4096;  // per-workgroup call counters of the fused GEMV (workgroups per launch)
 constexpr long long TPRES_REGION = 64 * 64 * 4;  // up to 64 rows x 64 columns x 2 bf16 per 8-byte granule
@@ -101,6 +113,14 @@ int gemm_argmax(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int
 size_t gemm_argmax_workspace_floats(int M, int N);
 // first max per row over [M][P] (value, index) float2 partials
 int argmax_partials(const float* part, int P, int M, int32_t* idx, float* val, hipStream_t s);
+// scoring lm_head: GEMM + log-sum-exp epilogue. Per row of this weight shard: tgt = the logit at column
+// targets[row] - col_offset (0 where that is outside [0, N)), mx = the row maximum, se = sum exp(logit - mx); the fp32
+// logits are never written. ws >= gemm_logprob_workspace_floats(M, N) floats. -1 where gemm_plan() has no MODE_LOGPROB
+// plan for the shape (the caller then runs the GEMM and logprob_rows).
+int gemm_logprob(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int M, int N, int K, float rms_eps,
+                 const int32_t* targets, int col_offset, float* tgt, float* mx, float* se, hipStream_t s,
+                 float* rms_ws = nullptr, size_t rms_ws_floats = 0);
+size_t gemm_logprob_workspace_floats(int M, int N);
 
 int rope_kv_write(const bf16_t* qkv, const float* table, int table_len, const int32_t* positions, bf16_t* kc,
                   bf16_t* vc, const int32_t* slot, int M, int S, int H, int Hkv, int Dh, int T, bf16_t* q_out,
@@ -141,6 +161,9 @@ int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int3
                  hipStream_t s);
 
 int argmax(const float* logits, int B, int V, int32_t* idx, float* val, hipStream_t s);
+// the (tgt, mx, se) triple of gemm_logprob from stored fp32 logits [B, V]
+int logprob_rows(const float* logits, int B, int V, const int32_t* targets, int col_offset, float* tgt, float* mx,
+                 float* se, hipStream_t s);
 // top-k / top-p sampler (topk_sample.hip): cv/ci [B, topk_chunks(V) * K] candidates
 int topk_chunks(int V);
 int topk_chunk(const float* logits, int B, int V, int K, int idx_offset, float* cv, int32_t* ci, hipStream_t s);

@@ -60,6 +60,53 @@ int argmax(const float* logits, int B, int V, int32_t* idx, float* val, hipStrea
   return 0;
 }
 
+// Scoring from stored fp32 logits (the unfused form of gemm_logprob, gemm.hip): one workgroup per row; tgt = the logit
+// at column targets[row] - col_offset (0 where that is outside [0, V): an ignored label, another rank's shard), mx =
+// the row maximum, se = sum exp(logit - mx). Two passes over the row (the second one reads it from the caches), fixed
+// reduction order.
+__global__ void __launch_bounds__(1024)
+    logprob_rows_kernel(const float* __restrict__ logits, int V, const int32_t* __restrict__ targets, int col_offset,
+                        float* __restrict__ tgt, float* __restrict__ mx, float* __restrict__ se) {
+  __shared__ float sm[16];
+  __shared__ float ssum[16];
+  constexpr float LOG2E = 1.4426950408889634f;
+  const int row = blockIdx.x;
+  const float* x = logits + (size_t)row * V;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6, nw = (blockDim.x + 63) >> 6;
+  float m = -INFINITY;
+  for (int i = threadIdx.x; i < V; i += blockDim.x) m = fmaxf(m, x[i]);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
+  if (lane == 0) sm[wid] = m;
+  __syncthreads();
+  m = sm[0];
+  for (int w = 1; w < nw; ++w) m = fmaxf(m, sm[w]);
+  float s = 0.f;
+  if (m != -INFINITY) {  // (never inf - inf)
+    for (int i = threadIdx.x; i < V; i += blockDim.x) s += __builtin_amdgcn_exp2f((x[i] - m) * LOG2E);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) ssum[wid] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < nw; ++w) s += ssum[w];
+    const int col = targets[row] - col_offset;
+    tgt[row] = col >= 0 && col < V ? x[col] : 0.f;
+    mx[row] = m;
+    se[row] = s;
+  }
+}
+
+int logprob_rows(const float* logits, int B, int V, const int32_t* targets, int col_offset, float* tgt, float* mx,
+                 float* se, hipStream_t s) {
+  if (B <= 0) return 0;
+  if (V <= 0) return -1;
+  logprob_rows_kernel<<<B, 1024, 0, s>>>(logits, V, targets, col_offset, tgt, mx, se);
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
 __global__ void decode_update_kernel(const int32_t* __restrict__ nxt, int32_t* __restrict__ finished,
                                      int32_t* __restrict__ sequences, int32_t* __restrict__ cur_len,
                                      int32_t* __restrict__ tokens, int32_t* __restrict__ positions,

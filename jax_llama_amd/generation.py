@@ -14,7 +14,7 @@ what is returned everywhere (token ids are identical on all ranks by constructio
 """
 from __future__ import annotations
 
-from typing import Any, List, Optional, Union
+from typing import Any, List, Optional, Tuple, Union
 
 import torch
 
@@ -50,6 +50,37 @@ class LLaMA:
         # the reference's output constraint P("dp", None) keeps the batch split across dp replicas;
         # here every replica gets the whole batch back (all-gather over the dp group when there is one)
         return gather_dp(out.sequences, self.mesh)
+
+    def loglikelihood(self, pairs: List[Tuple[str, str]]) -> List[Tuple[float, bool]]:
+        """``(log p(continuation | context), continuation is what greedy decoding would produce)`` per
+        ``(context, continuation)`` pair -- the evaluation-harness request behind multiple-choice tasks. The context is
+        encoded with BOS, the continuation without; rows are left-padded and carry an explicit length mask (no token
+        id stands for padding). One ``model.score`` call; with a mesh every replica scores every pair. A pair longer
+        than ``max_sequence_length``, the context the model was trained for, is an error here (``score`` itself, like
+        ``generate``, goes as far as the RoPE table)."""
+        tok = self.tokenizer
+        enc = [(tok.encode(c, bos=True, eos=False), tok.encode(x, bos=False, eos=False)) for c, x in pairs]
+        if not enc:
+            return []
+        longest = max(len(c) + len(x) for c, x in enc)
+        limit = self.model.config.max_sequence_length
+        if longest > limit:
+            raise ValueError(f"loglikelihood: a pair of {longest} tokens exceeds max_sequence_length ({limit})")
+        width = max(longest, 2)  # (score needs two positions; a lone BOS row is padded)
+        tokens = torch.zeros(len(enc), width, dtype=torch.int32)
+        mask = torch.zeros(len(enc), width, dtype=torch.int32)
+        for i, (c, x) in enumerate(enc):
+            row = c + x
+            tokens[i, width - len(row):] = torch.tensor(row, dtype=torch.int32)
+            mask[i, width - len(row):] = 1
+        out = self.model.score(tokens, attention_mask=mask)
+        lp, greedy = out.token_logprobs.double().cpu(), out.is_greedy.cpu()
+        res = []
+        for i, (c, x) in enumerate(enc):
+            n = len(x)  # the continuation's tokens are the row's last n: entries width-1-n .. width-2
+            res.append((float(lp[i, width - 1 - n:].sum()) if n else 0.0,
+                        bool(greedy[i, width - 1 - n:].all()) if n else True))
+        return res
 
     def generate_from_str(self, prompts: List[str], max_gen_len: int, temperature: float = 0.8,
                           top_p: float = 0.95, seed: int = 0) -> List[str]:

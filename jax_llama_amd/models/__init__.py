@@ -1,5 +1,5 @@
 from .kv_cache import KVCache
-from .llama import BaseModelOutput, CausalLMOutput, LLaMAForCausalLM, LLaMAModel, mask_to_kv_start
+from .llama import BaseModelOutput, CausalLMOutput, LLaMAForCausalLM, LLaMAModel, ScoreOutput, mask_to_kv_start
 from .modules import LLaMAAttention, LLaMABlock, LLaMABlockCollection, LLaMAMLP
 from .weights import PackedLinear
 
@@ -14,4 +14,4 @@ FlaxLLaMABlockCollection = LLaMABlockCollection
 __all__ = ["KVCache", "LLaMAForCausalLM", "LLaMAModel", "FlaxLLaMAForCausalLM", "FlaxLLaMAModel",
            "LLaMAAttention", "LLaMAMLP", "LLaMABlock", "LLaMABlockCollection", "FlaxLLaMAAttention",
            "FlaxLLaMAMLP", "FlaxLLaMABlock", "FlaxLLaMABlockCollection",
-           "CausalLMOutput", "BaseModelOutput", "PackedLinear", "mask_to_kv_start"]
+           "CausalLMOutput", "BaseModelOutput", "ScoreOutput", "PackedLinear", "mask_to_kv_start"]

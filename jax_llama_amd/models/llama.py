@@ -68,6 +68,20 @@ class CausalLMOutput:
 
 
 @dataclass
+class ScoreOutput:
+    """``LLaMAForCausalLM.score``: entry ``[b, t-1]`` belongs to token ``t`` of row ``b`` given the tokens before it."""
+
+    token_logprobs: torch.Tensor  # (B, S-1) fp32: log p(labels[b, t] | input_ids[b, :t]); 0 where ``mask`` is false
+    is_greedy: torch.Tensor       # (B, S-1) bool: the label is a maximum of its row of logits; true where masked out
+    mask: torch.Tensor            # (B, S-1) bool: both positions attended and the label is not ``ignore_index``
+
+    def __getitem__(self, k):
+        if isinstance(k, int):
+            return (self.token_logprobs, self.is_greedy, self.mask)[k]
+        return getattr(self, k)
+
+
+@dataclass
 class BaseModelOutput:
     last_hidden_state: torch.Tensor = None
     hidden_states: Optional[Tuple[torch.Tensor, ...]] = None
@@ -348,19 +362,23 @@ class LLaMAForCausalLM:
     def forward_tokens(self, ids: torch.Tensor, positions: torch.Tensor, cache: KVCache, slot0,
                        kv_start: torch.Tensor, key_mask: Optional[torch.Tensor] = None,
                        logits_mode: str = "last", collect_hidden: bool = False,
-                       collect_attn: bool = False):
+                       collect_attn: bool = False, targets: Optional[torch.Tensor] = None):
         """Run all layers for ``ids [B, S]`` placed at cache slots ``slot0 .. slot0+S-1``.
 
         ``slot0``: int or device int32[1] tensor (graph capture). Returns
         ``(logits_local, h, hidden_states, attentions)`` where logits are this rank's
         vocab shard: ``[B, V/tp]`` ("last"), ``[B*S, V/tp]`` ("all"), None ("none"), or the
-        shard's greedy ``(idx int32[B], val fp32[B])`` of the last position ("argmax")."""
+        shard's greedy ``(idx int32[B], val fp32[B])`` of the last position ("argmax"), or the shard's scoring
+        triple ``(tgt, mx, se)``, fp32 ``[B*S]`` each, of every position against the global token ids ``targets``
+        int32 ``[B*S]`` ("logprob", ``ops.linear_logprob``: no logits are materialised)."""
+        if (logits_mode == "logprob") != (targets is not None):
+            raise ValueError("logits_mode='logprob' takes `targets` (and no other mode does)")
         with ops.autotune.tp_scope(self.comm):  # TP: rank 0 picks the kernel plans for every rank
             return self._forward_tokens(ids, positions, cache, slot0, kv_start, key_mask, logits_mode,
-                                        collect_hidden, collect_attn)
+                                        collect_hidden, collect_attn, targets)
 
     def _forward_tokens(self, ids, positions, cache, slot0, kv_start, key_mask, logits_mode, collect_hidden,
-                        collect_attn):
+                        collect_attn, targets=None):
         b, s = ids.shape
         d = self.config.hidden_size
         # residual stream: fp32 h plus its bf16 mirror hb (the A operand of every projection
@@ -371,6 +389,12 @@ class LLaMAForCausalLM:
                                     output_hidden_states=collect_hidden, output_attentions=collect_attn)
         if logits_mode == "none":
             logits = None
+        elif logits_mode == "logprob":  # scoring: this rank's (tgt, mx, se) per position, reduced in the GEMM epilogue
+            off = self.tp_rank * self.vocab_local
+            if self.precision == "highest":
+                logits = ops.linear_f32_logprob(self.final_norm(h), self.lm_head_f32, targets, col_offset=off)
+            else:
+                logits = ops.linear_logprob(hb, self.lm_head, targets, rms_eps=self.eps, col_offset=off)
         elif self.precision == "highest":  # fp32 lm_head weights + fp32 GEMM (reference model.py:698-736)
             hl = h if logits_mode == "all" else h.reshape(b, s, d)[:, -1].contiguous()
             logits = ops.linear_f32(self.final_norm(hl), self.lm_head_f32)
@@ -453,6 +477,66 @@ class LLaMAForCausalLM:
         out = CausalLMOutput(logits=logits, past_key_values=past_key_values, hidden_states=hs,
                              attentions=tuple(attns) if oa else None)
         return out if rd else out.to_tuple()
+
+    def score(self, input_ids, attention_mask=None, labels=None, ignore_index: int = -100) -> ScoreOutput:
+        """Log-probabilities the model gives to tokens the caller already has (perplexity, multiple choice,
+        reranking): entry ``[b, t-1]`` of every field is for ``labels[b, t]`` (default: ``input_ids``) given
+        ``input_ids[b, :t]``, from the hidden state at ``t-1``. No ``(B, S, V)`` logits exist at any time: each
+        rank's lm_head GEMM reduces its vocab shard to ``(target logit, max, sum of exponentials)`` per position
+        (``ops.linear_logprob``), under TP the triples are all-gathered and combined in rank order (identical bits on
+        every rank). Positions and key masking follow ``DecodeEngine.prefill`` (``cumsum(mask) - 1``,
+        ``mask_to_kv_start``); rows run in chunks of at most ``runtime.engine.PREFILL_TOKENS`` tokens, each with its
+        own transient KV cache. Labels at scored positions must be in ``[0, vocab_size)`` or ``ignore_index``."""
+        from ..runtime import engine as _engine
+        ids = _t(input_ids).to("cpu", torch.int64)
+        if ids.dim() != 2 or ids.shape[1] < 2:
+            raise ValueError(f"score: input_ids must be (B, S) with S >= 2, got {tuple(ids.shape)}")
+        b, s = ids.shape
+        # the limit of init_cache, i.e. of __call__ and generate: what the RoPE table covers (token-level callers may
+        # run past the trained context on purpose; the string-level LLaMA.loglikelihood holds to max_sequence_length)
+        if s > self.rope_length:
+            raise ValueError(f"score: {s} positions exceed the RoPE table ({self.rope_length}); "
+                             "raise config.max_sequence_length")
+        lab = ids if labels is None else _t(labels).to("cpu", torch.int64)
+        if lab.shape != ids.shape:
+            raise ValueError(f"score: labels {tuple(lab.shape)} must have input_ids' shape {tuple(ids.shape)}")
+        if attention_mask is None:
+            mask = torch.ones(b, s, dtype=torch.int32)
+        else:
+            mask = _t(attention_mask).to("cpu").to(torch.int32)
+            if mask.shape != ids.shape:
+                raise ValueError(f"score: attention_mask {tuple(mask.shape)} must have input_ids' shape "
+                                 f"{tuple(ids.shape)}")
+        attended = mask != 0
+        valid = attended[:, :-1] & attended[:, 1:] & (lab[:, 1:] != ignore_index)
+        nxt = lab[:, 1:]
+        if bool((valid & ((nxt < 0) | (nxt >= self.config.vocab_size))).any()):
+            raise ValueError(f"score: labels must be in [0, {self.config.vocab_size}) or ignore_index "
+                             f"({ignore_index})")
+        targets = torch.full((b, s), -1, dtype=torch.int32)  # (-1: scored by nobody; the last position has no label)
+        targets[:, :-1] = torch.where(valid, nxt, torch.full_like(nxt, -1)).to(torch.int32)
+        dev = self.device
+        ids_d = ids.to(dev, torch.int32)
+        pos_d = (mask.cumsum(-1) - 1).to(torch.int32).to(dev)
+        tgt_d = targets.to(dev)
+        kv_start, key_mask = mask_to_kv_start(mask, dev)
+        rows = max(1, _engine.PREFILL_TOKENS // s)
+        parts = []
+        for b0 in range(0, b, rows):
+            b1 = min(b, b0 + rows)
+            cache = KVCache(self.config.num_hidden_layers, b1 - b0, self.n_kv_heads, s, self.head_dim, dev)
+            km = key_mask[b0:b1] if key_mask is not None else None
+            triple, *_ = self.forward_tokens(ids_d[b0:b1], pos_d[b0:b1].contiguous(), cache, 0, kv_start[b0:b1], km,
+                                             logits_mode="logprob", targets=tgt_d[b0:b1].reshape(-1))
+            parts.append(torch.stack(triple))
+        local = parts[0] if len(parts) == 1 else torch.cat(parts, 1)  # [3, B*S]: tgt, mx, se of this rank's shard
+        g = self.comm.all_gather(local)  # [tp, 3, B*S], rank order
+        lp, _, is_max = ops.logprob_combine(g[:, 0], g[:, 1], g[:, 2])
+        valid_d = valid.to(lp.device)
+        lp = lp.reshape(b, s)[:, :-1]
+        is_max = is_max.reshape(b, s)[:, :-1]
+        return ScoreOutput(token_logprobs=torch.where(valid_d, lp, torch.zeros_like(lp)),
+                           is_greedy=is_max | ~valid_d, mask=valid_d)
 
     def prepare_inputs_for_generation(self, input_ids, max_length: int, attention_mask=None):
         """Reference ``model.py:748-767``: cache, extended (B, max_length) mask with the

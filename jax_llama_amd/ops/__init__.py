@@ -706,6 +706,91 @@ def linear_argmax(x: torch.Tensor, w, rms_eps: Optional[float] = None):
     return idx, val
 
 
+# ---------------------------------------------------------------------------------- scoring
+MODE_LOGPROB = 10  # csrc/kernels/gemm_plan.h (gemm_logprob only)
+LOGPROB_CHUNK_BYTES = 256 << 20  # the unfused form's transient fp32 logits, per row chunk
+
+
+def logprob(logits: torch.Tensor, targets: torch.Tensor, col_offset: int = 0):
+    """Scoring triple ``(tgt, mx, se)`` (fp32 ``[M]`` each) of one vocab shard's stored fp32 logits ``[M, V]``:
+    the logit at column ``targets - col_offset`` (0 where that is outside ``[0, V)``: an ignored label, a column of
+    another rank's shard), the row maximum, and ``sum exp(logit - mx)``. See ``logprob_combine``."""
+    if not _is_gpu(logits):
+        return ref.logprob(logits, targets, col_offset)
+    assert logits.dim() == 2 and logits.dtype == torch.float32 and logits.is_contiguous(), (logits.shape, logits.dtype)
+    m = logits.shape[0]
+    out = torch.empty(3, m, dtype=torch.float32, device=logits.device)
+    ext().logprob_rows(logits, targets.reshape(-1).to(torch.int32), int(col_offset), out[0], out[1], out[2])
+    return out[0], out[1], out[2]
+
+
+def logprob_fused(x: torch.Tensor, w, rms_eps: Optional[float] = None) -> bool:
+    """Whether ``linear_logprob`` runs the GEMM with the log-sum-exp in its epilogue for this call (the one rule is
+    gemm_plan()'s: gemm4's 256 x 256 tile without a K split, from ARGMAX_FUSED_MIN_M rows)."""
+    if not _is_gpu(x) or x.shape[0] < ARGMAX_FUSED_MIN_M:
+        return False
+    rms = rms_eps is not None
+    return ext().gemm_plan_check(x.shape[0], w.n, w.k, MODE_LOGPROB, rms, 1, 0, rms) == 0
+
+
+def _logprob_chunks(m: int, n: int):
+    rows = max(1, LOGPROB_CHUNK_BYTES // (4 * n))
+    return [(r0, min(m, r0 + rows)) for r0 in range(0, m, rows)]
+
+
+def linear_logprob(x: torch.Tensor, w, targets: torch.Tensor, rms_eps: Optional[float] = None, col_offset: int = 0):
+    """Scoring triple ``(tgt, mx, se)`` of ``[inv_rms(x) *] x @ W^T`` (the lm_head; ``w`` one vocab shard whose
+    column 0 is global column ``col_offset``) at the global target columns ``targets`` int32 ``[M]``. On the GPU the
+    reduction runs in the GEMM epilogue and the fp32 logits never reach HBM (``gemm_logprob``) wherever
+    ``logprob_fused``; else ``linear`` + ``logprob`` over row chunks of at most LOGPROB_CHUNK_BYTES of logits."""
+    if not _is_gpu(x):
+        return ref.linear_logprob(x, w.dense(), targets, rms_eps, col_offset)
+    m = x.shape[0]
+    assert x.is_contiguous() and x.shape[1] == w.k, (x.shape, w.k)
+    tg = targets.reshape(-1).to(torch.int32)
+    assert tg.numel() == m, (tg.shape, m)
+    out = torch.empty(3, m, dtype=torch.float32, device=x.device)
+    if logprob_fused(x, w, rms_eps):
+        e = ext()
+        xb = x if x.dtype == BF16 else x.to(BF16)
+        ws = workspace.get("gemm_logprob", e.gemm_logprob_workspace(m, w.n), torch.float32, x.device)
+        e.gemm_logprob(xb, w.weight, w.n, w.k, ws, -1.0 if rms_eps is None else float(rms_eps), tg, int(col_offset),
+                       out[0], out[1], out[2], _rms_ws(x, rms_eps is not None, 1))
+    else:
+        for r0, r1 in _logprob_chunks(m, w.n):
+            logits = linear(x[r0:r1], w, rms_eps, out_dtype=torch.float32)
+            ext().logprob_rows(logits, tg[r0:r1], int(col_offset), out[0, r0:r1], out[1, r0:r1], out[2, r0:r1])
+    return out[0], out[1], out[2]
+
+
+def linear_f32_logprob(x: torch.Tensor, w: torch.Tensor, targets: torch.Tensor, col_offset: int = 0):
+    """``linear_logprob`` for the fp32 lm_head (precision='highest'): ``linear_f32`` + ``logprob`` over row chunks."""
+    m = x.shape[0]
+    tg = targets.reshape(-1).to(torch.int32)
+    parts = [logprob(linear_f32(x[r0:r1], w), tg[r0:r1], col_offset) for r0, r1 in _logprob_chunks(m, w.shape[0])]
+    return tuple(torch.cat([p[i] for p in parts]) for i in range(3))
+
+
+def logprob_combine(tgt: torch.Tensor, mx: torch.Tensor, se: torch.Tensor):
+    """Per-shard scoring triples ``[M]`` or stacked ``[tp, M]`` (rank order) -> ``(logprob, lse, is_max)``:
+    ``Mx = max_r mx_r``, ``S = sum_r se_r exp(mx_r - Mx)`` summed in rank order, ``lse = Mx + log S``, ``logprob =
+    sum_r tgt_r - lse`` (one rank holds the target, the others contribute 0) and ``is_max = (sum_r tgt_r == Mx)``: the
+    target is a maximum of its row, i.e. what greedy decoding picks up to ties. An empty shard ``(-inf, 0)`` is the
+    identity; the same inputs give the same bits on every rank."""
+    if tgt.dim() == 1:
+        tgt, mx, se = tgt[None], mx[None], se[None]
+    tgt, mx, se = tgt.float(), mx.float(), se.float()
+    big = mx.max(0).values
+    safe = torch.where(torch.isinf(big), torch.zeros_like(big), big)  # (never inf - inf)
+    total = torch.zeros_like(big)
+    t = torch.zeros_like(big)
+    for r in range(mx.shape[0]):
+        total = total + se[r] * torch.exp(mx[r] - safe)
+        t = t + tgt[r]
+    lse = big + torch.log(total)
+    return t - lse, lse, t == big
+
+
 SAMPLER_MAX_K = 64
 
 

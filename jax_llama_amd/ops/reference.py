@@ -233,6 +233,25 @@ def argmax(logits: torch.Tensor) -> torch.Tensor:
     return logits.float().argmax(-1).to(torch.int32)  # first max index, like jnp.argmax
 
 
+def logprob(logits: torch.Tensor, targets: torch.Tensor, col_offset: int = 0):
+    """Scoring triple of one vocab shard's logits ``[M, V]``: ``tgt`` = the logit at column ``targets - col_offset``
+    (0 where that is outside ``[0, V)``: an ignored label, another rank's shard), ``mx`` = the row maximum, ``se`` =
+    ``sum exp(logit - mx)``; fp32 ``[M]`` each. ``log p(target) = sum_r tgt_r - lse`` (``ops.logprob_combine``)."""
+    x = logits.float()
+    col = targets.to(torch.int64).reshape(-1) - int(col_offset)
+    ok = (col >= 0) & (col < x.shape[1])
+    picked = x.gather(1, col.clamp(0, x.shape[1] - 1).unsqueeze(1)).squeeze(1)
+    tgt = torch.where(ok, picked, torch.zeros_like(picked))
+    mx = x.max(-1).values
+    se = torch.exp(x - mx.unsqueeze(1)).sum(-1)
+    return tgt, mx, se
+
+
+def linear_logprob(x, w_dense, targets, rms_eps=None, col_offset: int = 0):
+    """fp32 ``linear`` followed by the scoring triple."""
+    return logprob(linear(x, w_dense, rms_eps, torch.float32), targets, col_offset)
+
+
 def top_k_top_p_filter(logits: torch.Tensor, temperature: float, top_k: int, top_p: float) -> torch.Tensor:
     """Returns warped logits with filtered entries at -inf (FlaxTemperature/TopK/TopP)."""
     x = logits.float()
