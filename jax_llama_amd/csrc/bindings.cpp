@@ -154,8 +154,8 @@ void check_linear_out(const Tensor& out, int64_t m, int64_t n, int64_t mode) {
     check(out.scalar_type() == torch::kBFloat16 || out.scalar_type() == torch::kFloat32, "out must be bf16/fp32");
 }
 
-// packed-layout activation copy (common.h pack_off): bf16, >= ceil(M/16 -> 1, 2 or 4 m-tiles) * 16 rows of `cols`
-int64_t packed_rows(int64_t m) { return m <= 16 ? 16 : (m <= 32 ? 32 : 64); }
+// packed-layout activation copy (common.h pack_off): bf16, >= the GEMV's m-tiles (1, 2 or 4) * 16 rows of `cols`
+int64_t packed_rows(int64_t m) { return 16 * jla::gemv_m_tiles((int)m); }
 jla::bf16_t* packed_ptr(const c10::optional<Tensor>& t, int64_t m, int64_t cols, const char* what) {
   if (!t.has_value()) return nullptr;
   check_gpu(*t, what);
@@ -164,39 +164,36 @@ jla::bf16_t* packed_ptr(const c10::optional<Tensor>& t, int64_t m, int64_t cols,
   return bf(*t);
 }
 
-// Decode linear dispatch (gemv.hip dispatch_nt). variant: 0 / 1 = K-split GEMV (4 waves at M <= 16), 5 / 6 = 4 / 2
-// tiles per workgroup, 10 = 2 tiles with a doubled ring, 20 = 2 tiles x 8 waves, 16 = split-K GEMV, packed-x 12 / 15 /
-// 18 / 21 / 22 / 26 (variant ids of removed forms are not reused: profiles/r4_variant_pruning.md).
+// The plan of a decode-GEMV call, or the rule that refuses it (kernels/gemv_plan.h: the variant table and every rule)
+jla::GemvPlan skinny_plan(int64_t m, int64_t n, int64_t k, int64_t mode, bool f32, bool x_packed, int64_t variant) {
+  const jla::GemvPlanResult r = jla::gemv_plan((int)m, (int)n, (int)k, (int)mode, f32, x_packed, (int)variant);
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: decode GEMV variant ", variant, ": ", r.why, " (see gemv_plan.h)");
+  return r.plan;
+}
+
+// Decode linear dispatch (gemv.hip linear_skinny); the variant ids: kernels/gemv_plan.h
 void run_skinny(const Tensor& x, const Tensor& w, int64_t n, int64_t k, void* out, int64_t mode, double rms_eps,
                 bool accumulate, bool out_f32, const jla::QKVArgs* qa, int64_t variant, const Tensor& ws,
                 const Tensor& tickets, const jla::bf16_t* x_packed = nullptr) {
   const int64_t m = x.size(0);
   const bool f32 = x.scalar_type() == torch::kFloat32;
-  if (variant == 0) variant = 1;
-  const bool xp_variant = jla::gemv_xp_variant((int)variant);
-  check(xp_variant == (x_packed != nullptr), "packed-x variants (12, 15, 18, 21, 22, 26) need x_packed, the others must not");
-  check(!xp_variant || !f32, "packed-x variants read bf16 activations");
-  check(!(xp_variant && mode == 2 && variant == 12), "SwiGLU packed-x variants: 15, 18, 21, 22, 26");
-  check(variant == 1 || variant == 5 || variant == 6 || variant == 10 || variant == 16 || variant == 20 || xp_variant,
-        "unknown decode GEMV variant");
-  {
-    jla::QKVArgs qs = *qa;
-    if (jla::gemv_split_variant((int)variant)) {
-      // split-K GEMV: partial slabs + self-resetting tickets (the shared skinny workspace, sized for both)
-      check_gpu(ws, "ws");
-      check_gpu(tickets, "tickets");
-      check(ws.scalar_type() == torch::kFloat32 && tickets.scalar_type() == torch::kInt32, "ws/tickets dtypes");
-      check((size_t)ws.numel() >= jla::gemv_split_workspace_floats(m, n) && ws.numel() < (1LL << 29) &&
-                tickets.numel() >= jla::gemv_split_tickets(n) && jla::gemv_split_tickets(n) > 0,
-            "split-K GEMV: workspace / tickets too small, or too many column groups");
-      qs.sk_ws = ptr<float>(ws);
-      qs.sk_tk = ptr<int32_t>(tickets);
-      qs.sk_ws_floats = (int)ws.numel();
-    }
-    rc(jla::linear_skinny(x_packed ? (const void*)x_packed : x.data_ptr(), f32, w.data_ptr(), out, m, n, k, mode,
-                          (float)rms_eps, accumulate, out_f32, &qs, variant, stream()),
-       "linear_skinny");
+  const jla::GemvPlan p = skinny_plan(m, n, k, mode, f32, x_packed != nullptr, variant);
+  jla::QKVArgs qs = *qa;
+  if (p.split) {
+    // split-K GEMV: partial slabs + self-resetting tickets (the shared skinny workspace, sized for both)
+    check_gpu(ws, "ws");
+    check_gpu(tickets, "tickets");
+    check(ws.scalar_type() == torch::kFloat32 && tickets.scalar_type() == torch::kInt32, "ws/tickets dtypes");
+    check((size_t)ws.numel() >= jla::gemv_split_workspace_floats(m, n) && ws.numel() < (1LL << 29) &&
+              tickets.numel() >= jla::gemv_split_tickets(n),
+          "split-K GEMV: workspace / tickets too small");
+    qs.sk_ws = ptr<float>(ws);
+    qs.sk_tk = ptr<int32_t>(tickets);
+    qs.sk_ws_floats = (int)ws.numel();
   }
+  rc(jla::linear_skinny(x_packed ? (const void*)x_packed : x.data_ptr(), f32, w.data_ptr(), out, m, n, k, mode,
+                        (float)rms_eps, accumulate, out_f32, &qs, variant, stream()),
+     "linear_skinny");
 }
 
 void linear_skinny(Tensor x, Tensor w, int64_t n, int64_t k, Tensor out, int64_t mode, double rms_eps,
@@ -215,7 +212,7 @@ void linear_skinny(Tensor x, Tensor w, int64_t n, int64_t k, Tensor out, int64_t
   // packed copy of the bf16 output (the residual's mirror / the SwiGLU activation): GEMV variants only
   qa.pack = packed_ptr(pack_out, m, mode == 2 ? n / 2 : n, "pack_out");
   check(!qa.pack || (mode == 1 || mode == 2), "pack_out: residual (mirror) or SwiGLU output only");
-  check(!qa.pack || (variant != 0 && variant != 7), "pack_out: GEMV variants only");
+  check(!qa.pack || variant != 0, "pack_out: name a GEMV variant");
   check(!qa.pack || mode != 1 || qa.res_bf16, "pack_out of a residual needs the mirror");
   run_skinny(x, w, n, k, out.data_ptr(), mode, rms_eps, accumulate, out.scalar_type() == torch::kFloat32, &qa,
              variant, ws, tickets, packed_ptr(x_packed, m, k, "x_packed"));
@@ -231,8 +228,7 @@ void linear_skinny_argmax(Tensor x, Tensor w, int64_t n, int64_t k, double rms_e
         "x must be fp32/bf16 [M, K]");
   const int64_t m = x.size(0);
   check(m <= SKINNY_MAX_M, "linear_skinny_argmax: M too large");
-  check(variant == 1 || variant == 5 || variant == 6 || variant == 10 || variant == 20,
-        "argmax: GEMV variants only (row-major x)");
+  skinny_plan(m, n, k, MODE_ARGMAX, x.scalar_type() == torch::kFloat32, false, variant);
   check_gpu(part, "part");
   check(part.scalar_type() == torch::kFloat32 && part.numel() >= m * (n / 16) * 2, "argmax partials too small");
   check_gpu(idx, "idx");
@@ -247,10 +243,8 @@ void linear_skinny_argmax(Tensor x, Tensor w, int64_t n, int64_t k, double rms_e
   rc(jla::argmax_partials(ptr<float>(part), n / 16, m, ptr<int32_t>(idx), ptr<float>(val), stream()), "argmax_partials");
 }
 
-// the decode workspace of the split-K GEMV variants (16 / 18 / 26): partial slabs + tickets
-py::tuple skinny_workspace(int64_t m, int64_t n, int64_t k, int64_t mode) {
-  (void)k;
-  (void)mode;
+// the decode workspace of the split-K GEMV variants: partial slabs + tickets
+py::tuple skinny_workspace(int64_t m, int64_t n) {
   return py::make_tuple((int64_t)jla::gemv_split_workspace_floats(m, n), (int64_t)jla::gemv_split_tickets(n));
 }
 
@@ -737,7 +731,6 @@ void linear_tp_residual(int64_t state, Tensor x, Tensor w, int64_t n, int64_t k,
   check(m >= 1 && m <= SKINNY_MAX_M, "linear_tp_residual: 1 <= M <= 64");
   check(h.scalar_type() == torch::kFloat32 && h.numel() == m * n && hb.scalar_type() == torch::kBFloat16 &&
             hb.numel() == m * n, "h fp32 / hb bf16 [M, N]");
-  check(variant != 0 && variant != 4 && variant != 7, "linear_tp_residual: GEMV variants only");
   void* st = reinterpret_cast<void*>(state);
   // one TPRES_REGION per workgroup (at most 4096 workgroups: the counters), inside one slot
   const int64_t groups = n / 16;  // upper bound (1 tile per workgroup)
@@ -747,7 +740,7 @@ void linear_tp_residual(int64_t state, Tensor x, Tensor w, int64_t n, int64_t k,
   qa.res_bf16 = bf(hb);
   qa.pack = packed_ptr(hb_pack, m, n, "hb_pack");
   qa.tp = jla::car_device(st);
-  // split-K variants (16 / 18 / 26) take the shared decode workspace: only the last arriver of a column group exchanges
+  // split-K variants take the shared decode workspace: only the last arriver of a column group exchanges
   run_skinny(x, w, n, k, h.data_ptr(), MODE_TPRESID, -1.0, true, true, &qa, variant, ws ? *ws : Tensor(),
              tickets ? *tickets : Tensor(), packed_ptr(x_packed, m, k, "x_packed"));
 }
@@ -838,6 +831,21 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     return jla::gemm_plan_check((int)m, (int)n, (int)k, (int)mode, rms, (int)ksplit, (int)tile, has_rms_ws, (int)n_body);
   }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("mode"), py::arg("rms"), py::arg("ksplit"), py::arg("tile"),
      py::arg("has_rms_ws"), py::arg("n_body") = 0);
+  // (rc, mt, nt, nw, deep, xp, ksplit) of a decode-GEMV call (kernels/gemv_plan.h): rc 0 and the resolved kernel form
+  // (mt 0: nothing to launch), or the code linear_skinny() would fail with
+  m.def("gemv_plan_check", [](int64_t m, int64_t n, int64_t k, int64_t mode, bool x_f32, bool x_packed,
+                              int64_t variant) {
+    const jla::GemvPlanResult r = jla::gemv_plan((int)m, (int)n, (int)k, (int)mode, x_f32, x_packed, (int)variant);
+    const jla::GemvPlan& p = r.plan;
+    return py::make_tuple(r.rc, p.mt, p.nt, p.nw, p.deep, p.xp, p.ksplit);
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("mode"), py::arg("x_f32"), py::arg("x_packed"),
+     py::arg("variant"));
+  m.def("gemv_variant_table", []() {  // {id: (packed x, split-K)}
+    py::dict t;
+    for (const jla::GemvVariant& v : jla::GEMV_VARIANTS) t[py::int_(v.id)] = py::make_tuple(v.xp, v.split);
+    return t;
+  });
+  m.attr("GEMV_SPLIT_MAX_GROUPS") = jla::GEMV_SPLIT_MAX_GROUPS;
   m.def("gemm_qkv_direct_ok", [](int64_t m, int64_t tile, int64_t k) {
     return jla::gemm_qkv_direct_ok((int)m, (int)tile, (int)k) != 0;
   });

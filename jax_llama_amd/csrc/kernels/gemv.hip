@@ -23,6 +23,8 @@
 //     interleaved [w1;w3] weight, or (QKV mode) rotates q/k pairs with RoPE and writes q plus the
 //     k/v cache rows at the device-side cache slot.
 // No atomics: results are deterministic and the residual add happens exactly once.
+#include <type_traits>
+
 #include "attn_mma.h"
 #include "car.h"
 #include "common.h"
@@ -479,108 +481,56 @@ static int launch_skinny(const void* x, const void* W, void* out, int M, int N, 
   return 0;
 }
 
-// waves per workgroup: 4 at M <= 16 (measured best on MI355X for every Llama-3-8B projection at M = 1 and 16), 8
-// above. (The 8 / 16-wave forms of the one-m-tile GEMV, variants 2 / 3, were never picked at a bench or latency
-// shape -- 8B, 70B MP 1, the TP8 rank proxy -- and were removed in round 4: profiles/r4_variant_pruning.md.)
-template <typename XT, int MT, int NT, int MODE>
-static int dispatch_nw(const void* x, const void* W, void* out, int M, int N, int K, float eps, int use_rms,
-                       int accumulate, int out_f32, const QKVArgs& qa, hipStream_t s) {
-  if constexpr (MT == 1)
-    return launch_skinny<XT, MT, NT, MODE, 4>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-  return launch_skinny<XT, MT, NT, MODE, 8>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-}
-
-template <typename XT, int MT, int MODE>
-static int dispatch_nt(const void* x, const void* W, void* out, int M, int N, int K, float eps, int use_rms,
-                       int accumulate, int out_f32, const QKVArgs& qa, int variant, hipStream_t s) {
-  // SwiGLU needs the gate/up tile pair in one workgroup; very wide outputs (lm_head, w1|w3) use
-  // 2 tiles per workgroup to halve the activation re-reads.
-  // variant 5 / 6: 4 waves with 4 / 2 tiles per workgroup (x re-reads / 4, / 2) for tuning; at MT > 1
-  // the activation fragments outnumber the weight fragments of a 1-tile workgroup, so these matter more.
-  {
-    if (variant == 5 && (N & 63) == 0)
-      return launch_skinny<XT, MT, 4, MODE, 4>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-    if (variant == 6)
-      return launch_skinny<XT, MT, 2, MODE, 4>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-    // variant 10 (bf16 activations, M > 16): 2 tiles per workgroup (as 6) with a doubled ring -- more weight +
-    // activation bytes in flight per wave for the latency-bound projections
-    if constexpr (MT > 1 && sizeof(XT) == 2) {
-      if (variant == 10)
-        return launch_skinny<XT, MT, 2, MODE, 4, 1>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-    }
-    // split-K variants (bf16 activations): K cut over 2 workgroups per column group (16; 18 on packed x), the last
-    // arriver sums the splits and runs the epilogue -- for projections with few column groups (tensor-parallel qkv
-    // shards, N = 1280 at Llama-3-70B MP 8: 80 one-tile workgroups leave most CUs idle).
-    // 1 tile per workgroup (SwiGLU: the gate/up pair), 4 waves at M <= 16, 8 above.
-    if constexpr (sizeof(XT) == 2 && MODE != MODE_ARGMAX) {
-      // 26: 4 tiles x 8 waves per workgroup on packed x with K over 4 workgroups -- the 4-tile x re-read ratio of 22/23
-      // for the narrow, deep projections at M = 17..64 (w2 at N = 4096: 64 column groups alone leave most CUs idle).
-      // The 4-wave forms with 2 / 4 splits never won a shape (profiles/r3_gemv_split4tile_candidates.jsonl).
-      if (variant == 26) {
-        if (N & 63) return -1;
-        return launch_skinny<XT, MT, 4, MODE, 8, 0, true, true>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32,
-                                                                qa, s, 4);
-      }
-      if (gemv_split_variant(variant)) {
-        constexpr int SNT = MODE == MODE_SWIGLU ? 2 : 1, SNW = MT == 1 ? 4 : 8;
-        const int ks = 2;  // (K over 4 lost to 2 on the 70B MP 8 qkv shard at M = 1 / 32: profiles/README.md round 5)
-        if (variant == 18)
-          return launch_skinny<XT, MT, SNT, MODE, SNW, 0, true, true>(x, W, out, M, N, K, eps, use_rms, accumulate,
-                                                                      out_f32, qa, s, ks);
-        return launch_skinny<XT, MT, SNT, MODE, SNW, 0, false, true>(x, W, out, M, N, K, eps, use_rms, accumulate,
-                                                                     out_f32, qa, s, ks);
-      }
-    }
-    // 2 tiles x 8 waves (20 row-major, 21 packed x): twice the bytes in flight per workgroup of the 2-tile variants
-    // for wide projections with few column groups (w1|w3 at Llama-3-70B MP 8: 224 workgroups of the SwiGLU pairs)
-    if (variant == 20)
-      return launch_skinny<XT, MT, 2, MODE, 8>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-    if constexpr (sizeof(XT) == 2) {
-      if (variant == 21)
-        return launch_skinny<XT, MT, 2, MODE, 8, 0, true>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-      // 4 tiles x 4 waves reading packed x (22): half the activation bytes per weight byte of the 2-tile variants,
-      // for wide projections at M = 17..64 (w1|w3: 1792 column tiles at Llama-3-8B)
-      if (variant == 22) {  // (x is the packed copy: never fall through to a row-major variant)
-        if (N & 63) return -1;
-        return launch_skinny<XT, MT, 4, MODE, 4, 0, true>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-      }
-    }
-    // packed-x variants (x is the packed copy, common.h pack_off, padded to MT * 16 rows): 12 = 1 tile x 8 waves,
-    // 15 = 2 tiles x 4 waves with a doubled ring (also the SwiGLU form)
-    if constexpr (sizeof(XT) == 2) {
-      if (variant == 15)
-        return launch_skinny<XT, MT, 2, MODE, 4, 1, true>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-      if constexpr (MODE != MODE_SWIGLU) {
-        if (variant == 12)
-          return launch_skinny<XT, MT, 1, MODE, 8, 0, true>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-      }
-    }
-  }
-  if constexpr (MODE == MODE_SWIGLU) {
-    return dispatch_nw<XT, MT, 2, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-  } else {
-    if (MODE != MODE_QKV && (N >> 4) >= 2048)
-      return dispatch_nw<XT, MT, 2, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-    return dispatch_nw<XT, MT, 1, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s);
-  }
-}
-
+// One decode-GEMV launch: the linear_skinny_kernel form a resolved plan (gemv_plan.h) names. Checks nothing itself;
+// the forms that do not exist are not instantiated: no packed-x or split-K form on fp32 x, no split under the argmax
+// epilogue, no one-tile form under SwiGLU (the gate / up pair shares a workgroup), the doubled row-major ring and the
+// 1 x 4 workgroup only where the resolver picks them (M > 16 / M <= 16). Why each form exists: the variant table of
+// gemv_plan.h; what was measured and dropped: profiles/r4_variant_pruning.md, r3_gemv_split4tile_candidates.jsonl
+// (4-wave 4-tile splits), profiles/README.md round 5 (K over 4 for 16 / 18).
 template <typename XT, int MODE>
-static int dispatch_mt(const void* x, const void* W, void* out, int M, int N, int K, float eps, int use_rms,
-                       int accumulate, int out_f32, const QKVArgs& qa, int variant, hipStream_t s) {
-  if (M <= 16) return dispatch_nt<XT, 1, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, variant, s);
-  if (M <= 32) return dispatch_nt<XT, 2, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, variant, s);
-  return dispatch_nt<XT, 4, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, variant, s);
-}
-
-// the fused TP epilogue reads the bf16 decode activations only (no fp32-input instantiation)
-template <typename XT>
-static int dispatch_tp(const void* x, const void* W, void* out, int M, int N, int K, float eps, int use_rms,
-                       int accumulate, const QKVArgs& qa, int variant, hipStream_t s) {
-  if constexpr (sizeof(XT) == 2) {
-    return dispatch_mt<XT, MODE_TPRESID>(x, W, out, M, N, K, eps, use_rms, accumulate, 1, qa, variant, s);
-  } else {
-    return -1;
+static int launch_plan(const void* x, const void* W, void* out, int M, int N, int K, float eps, int use_rms,
+                       int accumulate, int out_f32, const QKVArgs& qa, const GemvPlan& p, hipStream_t s) {
+  constexpr bool BF16 = sizeof(XT) == 2, PAIR = MODE == MODE_SWIGLU;
+#define JLA_FORM(NT, NW, ...)  /* (..., DEEP, XP, SPLIT) */                                                          \
+  return launch_skinny<XT, MT, NT, MODE, NW, ##__VA_ARGS__>(x, W, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, \
+                                                            s, p.ksplit)
+  const auto form = [&](auto mt) -> int {
+    constexpr int MT = decltype(mt)::value;
+    if constexpr (BF16) {
+      if constexpr (MODE != MODE_ARGMAX) {
+        if (p.split) {  // the forms of 16 / 18: tiles by the epilogue, waves by M
+          constexpr int SNT = PAIR ? 2 : 1, SNW = MT == 1 ? 4 : 8;
+          if (p.nt == 4) JLA_FORM(4, 8, 0, true, true);
+          if (p.xp) JLA_FORM(SNT, SNW, 0, true, true);
+          JLA_FORM(SNT, SNW, 0, false, true);
+        }
+      }
+      if (p.xp) {
+        if (p.nt == 4) JLA_FORM(4, 4, 0, true);
+        if (p.deep) JLA_FORM(2, 4, 1, true);
+        if (p.nt == 2) JLA_FORM(2, 8, 0, true);
+        if constexpr (!PAIR) JLA_FORM(1, 8, 0, true);
+      }
+      if constexpr (MT > 1) {
+        if (p.deep) JLA_FORM(2, 4, 1);
+      }
+    }
+    if (p.nt == 4) JLA_FORM(4, 4);
+    if (p.nt == 2 && p.nw == 4) JLA_FORM(2, 4);
+    if (p.nt == 2) JLA_FORM(2, 8);
+    if constexpr (!PAIR) {
+      if constexpr (MT == 1) {
+        if (p.nw == 4) JLA_FORM(1, 4);
+      }
+      JLA_FORM(1, 8);
+    }
+    return -1;  // (not a plan of gemv_plan())
+  };
+#undef JLA_FORM
+  switch (p.mt) {
+    case 1: return form(std::integral_constant<int, 1>{});
+    case 2: return form(std::integral_constant<int, 2>{});
+    default: return form(std::integral_constant<int, 4>{});
   }
 }
 
@@ -1141,44 +1091,40 @@ int linear_qkv_attn(const bf16_t* x, const void* W, int M, int N, int K, float r
   return -1;
 }
 
-size_t gemv_split_workspace_floats(int M, int N) {
-  const int groups = N >> 4;  // upper bound: 1 tile per column group
-  if (groups > GEMV_SPLIT_MAX_GROUPS || M < 1 || M > SKINNY_MAX_M) return 0;
-  const int mt = M <= 16 ? 1 : (M <= 32 ? 2 : 4);
-  return (size_t)groups * 4 * (mt * 256 + mt * 16);  // (variant 26: 4 tiles per group, K over 4)
-}
-int gemv_split_tickets(int N) { return (N >> 4) > GEMV_SPLIT_MAX_GROUPS ? 0 : (N >> 4); }
-
 int linear_skinny(const void* x, int x_is_f32, const void* W, void* out, int M, int N, int K, int mode,
                   float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, int variant, hipStream_t s) {
-  if (M <= 0) return 0;
-  if (M > SKINNY_MAX_M || (N & 15) || (K & 31)) return -1;
-  if (mode == MODE_SWIGLU && (N & 31)) return -1;
+  // (a packed-x id says that x is the packed copy: the bindings hold the id against the buffer they were given)
+  const GemvVariant* gv = gemv_variant(variant);
+  const GemvPlanResult r = gemv_plan(M, N, K, mode, x_is_f32 != 0, gv && gv->xp, variant);
+  if (r.rc != 0 || r.plan.mt == 0) return r.rc;
   if (mode == MODE_QKV && (!qkv || qkv->Dh % 16 || M % qkv->S)) return -1;
   if (mode == MODE_TPRESID && (!qkv || !qkv->tp)) return -1;
-  if (gemv_split_variant(variant) && (x_is_f32 || mode == MODE_ARGMAX)) return -1;
   const int use_rms = rms_eps >= 0.f;
   const float eps = use_rms ? rms_eps : 0.f;
   QKVArgs qa{};
   if (qkv) qa = *qkv;
-#define JLA_ARGS x, W, out, M, N, K, eps, use_rms, accumulate
-#define JLA_MODE(XT)                                                                                 \
-  switch (mode) {                                                                                    \
-    case MODE_STORE: return dispatch_mt<XT, MODE_STORE>(JLA_ARGS, out_f32, qa, variant, s);          \
-    case MODE_RESIDUAL: return dispatch_mt<XT, MODE_RESIDUAL>(JLA_ARGS, 1, qa, variant, s);          \
-    case MODE_SWIGLU: return dispatch_mt<XT, MODE_SWIGLU>(JLA_ARGS, 0, qa, variant, s);              \
-    case MODE_QKV: return dispatch_mt<XT, MODE_QKV>(JLA_ARGS, 0, qa, variant, s);                    \
-    case MODE_ARGMAX: return dispatch_mt<XT, MODE_ARGMAX>(JLA_ARGS, 0, qa, variant, s);              \
-    case MODE_TPRESID: return dispatch_tp<XT>(JLA_ARGS, qa, variant, s);                             \
-    default: return -1;                                                                              \
-  }
+#define JLA_MODE(XT, MODE, OUT_F32) \
+  case MODE: return launch_plan<XT, MODE>(x, W, out, M, N, K, eps, use_rms, accumulate, OUT_F32, qa, r.plan, s)
   if (x_is_f32) {
-    JLA_MODE(float)
+    switch (mode) {  // (no MODE_TPRESID: the fused TP epilogue reads the bf16 decode activations only)
+      JLA_MODE(float, MODE_STORE, out_f32);
+      JLA_MODE(float, MODE_RESIDUAL, 1);
+      JLA_MODE(float, MODE_SWIGLU, 0);
+      JLA_MODE(float, MODE_QKV, 0);
+      JLA_MODE(float, MODE_ARGMAX, 0);
+    }
   } else {
-    JLA_MODE(bf16_t)
+    switch (mode) {
+      JLA_MODE(bf16_t, MODE_STORE, out_f32);
+      JLA_MODE(bf16_t, MODE_RESIDUAL, 1);
+      JLA_MODE(bf16_t, MODE_SWIGLU, 0);
+      JLA_MODE(bf16_t, MODE_QKV, 0);
+      JLA_MODE(bf16_t, MODE_ARGMAX, 0);
+      JLA_MODE(bf16_t, MODE_TPRESID, 1);
+    }
   }
 #undef JLA_MODE
-#undef JLA_ARGS
+  return -1;
 }
 
 JLA_BOUNDS_ACCESSOR(gemv)

@@ -5,8 +5,7 @@
 #include <stdint.h>
 
 #include "gemm_plan.h"
-
-#define SKINNY_MAX_M 64
+#include "gemv_plan.h"
 
 namespace jla {
 typedef uint16_t bf16_t;
@@ -73,15 +72,11 @@ int linear_qkv_attn(const bf16_t* x, const void* W, int M, int N, int K, float r
                     int t_cap, int splits, int spl, hipStream_t s,  // spl 2: K of the qkv GEMV over 2 (qa.sk_ws/sk_tk)
                     const void* o_w = nullptr, float* o_h = nullptr, int o_n = 0, int o_k = 0, int o_mode = 0,
                     const QKVArgs* qo = nullptr);
+// Decode GEMV (gemv.hip): y = epilogue(x[M, K] @ W[N, K]^T), M <= 64, on the form the variant id names (gemv_plan.h:
+// the variant table, and gemv_plan(), every rule of a legal call; -1 is its code). x is the packed copy for a packed-x
+// id. -3: a split form's slabs (qkv->sk_ws / sk_tk, gemv_split_workspace_floats / gemv_split_tickets) are too small.
 int linear_skinny(const void* x, int x_is_f32, const void* W, void* out, int M, int N, int K, int mode,
                   float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, int variant, hipStream_t s);
-// split-K GEMV variants 16 / 18 / 26 (K over gridDim.y workgroups per column group, last arriver sums + epilogue): their slab
-// floats / tickets (0 when N has too many column groups for them)
-constexpr int GEMV_SPLIT_MAX_GROUPS = 1024;
-size_t gemv_split_workspace_floats(int M, int N);
-int gemv_split_tickets(int N);
-inline bool gemv_split_variant(int v) { return v == 16 || v == 18 || v == 26; }
-inline bool gemv_xp_variant(int v) { return v == 12 || v == 15 || v == 18 || v == 21 || v == 22 || v == 26; }
 int clock_probe(int iters, int grid, unsigned long long* out, hipStream_t s);  // [cycles, 100 MHz ticks]
 // Tiled MFMA GEMM (gemm.hip): y = epilogue(x[M, K] @ W[N, K]^T) on the kernel the tile id names (gemm_plan.h: the
 // tile table, and gemm_plan(), every rule of a legal call; the return codes -1 / -5 / -6 / -7 are its). ksplit > 1

@@ -28,7 +28,7 @@ MODE_RESIDUAL = 1
 MODE_SWIGLU = 2
 MODE_QKV = 3
 
-# GEMV tuning override (0 = built-in heuristic; 1/2/3 = 4/8/16 waves per workgroup)
+# GEMV tuning override (0 = tuned per shape; else a variant id of csrc/kernels/gemv_plan.h, or 7: the tiled GEMM)
 GEMV_VARIANT = int(os.environ.get("JLA_GEMV_VARIANT", "0"))
 
 
@@ -236,13 +236,13 @@ PACKED_X_MIN_M = int(os.environ.get("JLA_PACKED_X_MIN_M", "9"))
 PACKED_X_MAX_M = int(os.environ.get("JLA_PACKED_X_MAX_M", "64"))
 PACKED_ATT_MAX_M = int(os.environ.get("JLA_PACKED_ATT_MAX_M", "64"))  # attention output only, up to here
 SKINNY_M = 64  # decode GEMV rows (csrc: SKINNY_MAX_M): packed copies exist only on that path
-XP_VARIANTS = (12, 15, 18, 21, 22, 26)  # packed-x GEMV variants (18 / 26 split-K; 21 / 22: 2x8 / 4x4; 26: 4 tiles x 8
-#   waves, K over 4)
-SPLIT_VARIANTS = (16, 18, 26)  # split-K GEMV variants (the shared decode workspace holds their slabs)
+# the GEMV ids by kind (autotune.GEMV_VARIANTS, the Python copy of the table of csrc/kernels/gemv_plan.h): packed-x /
+# split-K (the shared decode workspace holds their slabs)
+XP_VARIANTS, SPLIT_VARIANTS = autotune.XP_VARIANTS, autotune.SPLIT_VARIANTS
 
 
 def packed_rows(m: int) -> int:
-    """Rows of a packed activation buffer: the GEMV's m-tiles (1, 2 or 4) x 16."""
+    """Rows of a packed activation buffer: the GEMV's m-tiles (1, 2 or 4; gemv_plan.h gemv_m_tiles) x 16."""
     return 16 if m <= 16 else (32 if m <= 32 else 64)
 
 
@@ -262,14 +262,10 @@ def _gpu_linear(x, w, out, mode, rms_eps, accumulate, mirror=None, x_packed=None
         v = 1  # (a plan that cannot pack: the GEMV writes the packed copy)
     if v == TILED:
         _tiled(e, x, w.weight, w.n, w.k, out, mode, rms_eps, accumulate, mirror, pack_out)
-    elif x_packed is not None or pack_out is not None:
+    else:
         ws, tk = _skinny_ws(e, m, w.n, w.k, mode, x.device)
         e.linear_skinny(x, w.weight, w.n, w.k, out, mode, -1.0 if rms_eps is None else float(rms_eps),
                         bool(accumulate), v, ws, tk, mirror, x_packed if v in XP_VARIANTS else None, pack_out)
-    else:
-        ws, tk = _skinny_ws(e, m, w.n, w.k, mode, x.device)
-        e.linear_skinny(x, w.weight, w.n, w.k, out, mode,
-                        -1.0 if rms_eps is None else float(rms_eps), bool(accumulate), v, ws, tk, mirror)
 
 
 def linear_tp_residual(x: torch.Tensor, w, h: torch.Tensor, hb: torch.Tensor, state: int,
@@ -283,7 +279,7 @@ def linear_tp_residual(x: torch.Tensor, w, h: torch.Tensor, hb: torch.Tensor, st
     assert x.dtype == BF16 and x.is_contiguous() and m <= e.SKINNY_MAX_M, (x.dtype, x.shape)
     # the exchange lives in the GEMV epilogue: tune among the GEMV variants (``pack_out`` excludes split-K / tiled)
     v = _variant(e, x, w, MODE_RESIDUAL, x_packed, pack_out=True)
-    if v == TILED:
+    if v not in autotune.GEMV_VARIANTS:  # (the tiled GEMM)
         v = 1
     ws = tk = None
     if v in SPLIT_VARIANTS:
@@ -309,7 +305,7 @@ def tiled_tp_residual(x: torch.Tensor, w, h: torch.Tensor, hb: torch.Tensor, sta
     return True
 
 
-TILED = 7  # decode-kernel "variant" id of the 128x128 MFMA GEMM (split-K for mid M)
+TILED = autotune.TILED_VARIANT  # 7: decode-kernel "variant" id of the 128x128 MFMA GEMM (split-K for mid M)
 # qkv projection without a K split (B = 2048 decode, prefill): RoPE + KV write in the GEMM epilogue (JLA_QKV_DIRECT=0:
 # plain GEMM + rope_kv_kernel, for A/B)
 QKV_DIRECT = os.environ.get("JLA_QKV_DIRECT", "1") != "0"
@@ -378,12 +374,12 @@ def _variant(e, x, w, mode, x_packed=None, pack_out=None, no_split=False) -> int
     xp_in, p_out = x_packed is not None, pack_out is not None
     if GEMV_VARIANT:
         v = GEMV_VARIANT
-        if (v in XP_VARIANTS and not xp_in) or (p_out and v == TILED and not _tiled_packs(
+        xp, split = autotune.GEMV_VARIANTS.get(v, (False, False))
+        if (xp and not xp_in) or (p_out and v == TILED and not _tiled_packs(
                 e, x.shape[0], w.n, w.k, x.device, mode, None if mode == MODE_RESIDUAL else 1e-5)) or (
-                v in SPLIT_VARIANTS and (
-                no_split or x.dtype != BF16 or w.n // 16 > autotune.SPLIT_MAX_GROUPS)):
+                split and (no_split or x.dtype != BF16 or w.n // 16 > autotune.SPLIT_MAX_GROUPS)):
             v = 1
-        if v == 12 and mode == MODE_SWIGLU:
+        if v == 12 and mode == MODE_SWIGLU:  # (12 has no SwiGLU form: 15 is it)
             v = 15
         return v
     m = x.shape[0]
@@ -402,11 +398,9 @@ def _variant(e, x, w, mode, x_packed=None, pack_out=None, no_split=False) -> int
         if v == TILED:
             _tiled(e, xx, wt, w.n, w.k, scratch, pmode, None if pmode == MODE_RESIDUAL else 1e-5, True, mirror,
                    pscratch if tiled_packs else None)
-        elif xp_in or p_out:
+        else:
             e.linear_skinny(xx, wt, w.n, w.k, scratch, pmode, 1e-5, True, v, ws, tk, mirror,
                             x_packed if v in XP_VARIANTS else None, pscratch)
-        else:
-            e.linear_skinny(xx, wt, w.n, w.k, scratch, pmode, 1e-5, True, v, ws, tk)
 
     return autotune.choose(e, x, w, pmode, run, xp_in=xp_in, pack_out=p_out, no_split=no_split,
                            tiled_packs=tiled_packs)
@@ -421,7 +415,7 @@ def _skinny_ws(e, m, n, k, mode, device):
     key = (m, n, k, mode)
     sz = _SK_SIZES.get(key)
     if sz is None:
-        sz = _SK_SIZES[key] = tuple(e.skinny_workspace(m, n, k, mode))
+        sz = _SK_SIZES[key] = tuple(e.skinny_workspace(m, n))
     floats, tickets = sz
     return (workspace.get("skinny", max(1, floats), torch.float32, device),
             workspace.get_zeroed("skinny_tickets", max(1, tickets), torch.int32, device))
@@ -646,9 +640,6 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
     return out
 
 
-_SLOT_CACHE = {}
-
-
 def _slot_tensor(slot0, device):
     if torch.is_tensor(slot0):
         return slot0
@@ -686,7 +677,9 @@ def linear_argmax(x: torch.Tensor, w, rms_eps: Optional[float] = None):
     if m <= ext().SKINNY_MAX_M and SKINNY_ARGMAX:
         e = ext()
         v = _variant(e, x, w, MODE_STORE, no_split=True)  # the logits GEMV's main loop: its tuned variant applies
-        if v in (1, 2, 3, 5, 6, 8, 9, 20):
+        # every row-major GEMV pick but 10 takes the fused epilogue (10 is legal there; whether it should is a speed
+        # question that wants a measurement): the others, and the tiled GEMM, run linear + argmax
+        if v in autotune.ROW_MAJOR_VARIANTS and v != 10:
             part = workspace.get("skinny_argmax", m * (w.n // 16) * 2, torch.float32, x.device)
             idx = torch.empty(m, dtype=torch.int32, device=x.device)
             val = torch.empty(m, dtype=torch.float32, device=x.device)

@@ -9,9 +9,9 @@ candidate on a rotating set of scratch weights (> Infinity Cache, so each call s
 as in a real decode step) and caches the winner. Never runs under hipGraph capture; shapes first
 seen during capture fall back to the static heuristic.
 
-Variants: 1 = GEMV 4 waves (1 or 2 tiles/WG), 5 = GEMV 4 tiles/WG, 6 = GEMV 2 tiles/WG, 10 = 2 tiles with a doubled
-register ring (M > 16, bf16 activations), 20 = 2 tiles x 8 waves, 16 = K over 2 workgroups, packed-x 12 / 15 / 18 / 21 /
-22 / 26, 7 = tiled MFMA GEMM with split-K (gemm.hip; a candidate for M > 16, always used for M > 64). ``JLA_GEMV_VARIANT`` pins one; ``JLA_AUTOTUNE=0`` disables tuning.
+Variants: the GEMV ids of ``csrc/kernels/gemv_plan.h`` (the table of forms, and every rule of a legal call) and 7, the
+tiled MFMA GEMM with split-K (gemm.hip; a candidate for M > 16, always used for M > 64). ``JLA_GEMV_VARIANT`` pins one;
+``JLA_AUTOTUNE=0`` disables tuning.
 
 Shipped picks: ``ops/tune_gfx950.json`` (measured on an MI355X for the bench, latency and tensor-parallel shapes) is
 loaded first, so plans are identical on every box and nothing is measured for those shapes; shapes it lacks are
@@ -164,35 +164,46 @@ def heuristic(m: int, n: int, k: int, mode: int) -> int:
     return 1
 
 
-def candidates(m: int, n: int, swiglu: bool = False, bf16_x: bool = True) -> Tuple[int, ...]:
+TILED_VARIANT = 7
+# id -> (packed x, split-K) of the decode GEMV variants: the one Python copy of the id table of
+# csrc/kernels/gemv_plan.h (``_C`` cannot be imported without the HIP runtime; tests/test_gemv_plan_gpu.py holds this,
+# SPLIT_MAX_GROUPS and ops.packed_rows equal to the extension's)
+GEMV_VARIANTS = {1: (False, False), 5: (False, False), 6: (False, False), 10: (False, False), 12: (True, False),
+                 15: (True, False), 16: (False, True), 18: (True, True), 20: (False, False), 21: (True, False),
+                 22: (True, False), 26: (True, True)}
+XP_VARIANTS = XP_CANDIDATES = tuple(v for v, (xp, _) in GEMV_VARIANTS.items() if xp)
+SPLIT_VARIANTS = SPLIT_GEMV = tuple(v for v, (_, split) in GEMV_VARIANTS.items() if split)
+ROW_MAJOR_VARIANTS = tuple(v for v, (xp, split) in GEMV_VARIANTS.items() if not xp and not split)
+SPLIT_MAX_GROUPS = 1024  # column groups (N / 16) a split form covers
+
+
+def gemv_candidates(e, m: int, n: int, mode: int, dtype, xp_in: bool, pack_out: bool, no_split: bool,
+                    tiled_packs: bool, k: Optional[int] = None) -> List[int]:
+    """The variants ``_measure`` times for this key, in measuring order (the order decides ties, and picks are
+    persisted). Tuning policy only; legality is not restated here: ``gemv_plan_check`` (csrc/kernels/gemv_plan.h) is
+    asked about each GEMV id, a packed-x id reading the packed copy where one exists (``k`` None: any depth every
+    split form accepts)."""
+    bf16_x = dtype == torch.bfloat16
     # M > 16: two or four activation m-tiles per weight fragment, so the 2/4-tile GEMV workgroups
     # (fewer activation re-reads) and the tiled MFMA GEMM win on some shapes (M=24..64 sweep,
     # profiles/r1_decode_m32_variants.jsonl: qkv -> 6, gate_up -> 5, down/lm_head -> 7 at M=32)
-    c = [1, 6]
-    if n % 64 == 0:
-        c.insert(1, 5)
-    if m > 16:
-        c.append(TILED_VARIANT)
-        if bf16_x:
-            # doubled hand-counted ring (4 waves, 2 tiles): at M > 16 the single ring keeps only 2 k-steps in flight
-            # per wave (profiles/r2_decode_m32_asm_ring.jsonl)
-            c.append(10)
-    if n // 32 < 512:
-        c.append(20)  # 2 tiles x 8 waves: few column groups (w1|w3 shards)
-    if bf16_x and n // 16 <= SPLIT_MAX_GROUPS:
-        # split-K GEMV (K over 2 workgroups per column group, in-kernel last-arriver sum): few column groups
-        c.append(16)
-    return tuple(c)
-
-
-SPLIT_MAX_GROUPS = 1024  # csrc GEMV_SPLIT_MAX_GROUPS
-SPLIT_GEMV = (16, 18, 26)  # split-K GEMV variants (gemv.hip gemv_split_variant)
-
-
-TILED_VARIANT = 7
-
-
-XP_CANDIDATES = (12, 15, 18, 21, 22, 26)  # packed-x GEMV variants (gemv.hip dispatch_nt; 18 / 26 split-K)
+    policy = {
+        5: n % 64 == 0,  # (else legal, but the default form: measured as 1)
+        # the tiled GEMM qualifies for a packed output when its split-K reduce epilogue writes the copy
+        TILED_VARIANT: m > 16 and (tiled_packs or not pack_out),
+        # doubled hand-counted ring: at M > 16 the single ring keeps only 2 k-steps in flight per wave
+        # (profiles/r2_decode_m32_asm_ring.jsonl); at M <= 16 or with fp32 x legal, but the default form
+        10: m > 16 and bf16_x,
+        20: n // 32 < 512,  # 2 tiles x 8 waves: few column groups (w1|w3 shards)
+        21: n // 32 < 512,
+        22: n // 64 >= 64,
+        26: m > 16 and n // 64 < 256,  # 4-tile split-K: narrow outputs only (few 64-column groups), M > 16
+    }
+    kk = 32 * 4 if k is None else k
+    return [c for c in (1, 5, 6, TILED_VARIANT, 10, 20, 16) + XP_CANDIDATES
+            if policy.get(c, True) and not (no_split and c in SPLIT_GEMV) and
+            (c == TILED_VARIANT or
+             e.gemv_plan_check(m, n, kk, mode, not bf16_x, xp_in and c in XP_CANDIDATES, c)[0] == 0)]
 
 
 def choose(e, x: torch.Tensor, w, mode: int, run, xp_in: bool = False, pack_out: bool = False,
@@ -207,20 +218,9 @@ def choose(e, x: torch.Tensor, w, mode: int, run, xp_in: bool = False, pack_out:
     v = _CACHE.get(key)
     if v is not None:
         return v
-    cands = list(candidates(m, w.n, swiglu=(mode == 2), bf16_x=(x.dtype == torch.bfloat16)))
-    if pack_out:  # the tiled GEMM qualifies when its split-K reduce epilogue writes the copy (``tiled_packs``)
-        cands = [c for c in cands if c != TILED_VARIANT or tiled_packs]
-    if xp_in and x.dtype == torch.bfloat16:
-        cands += [c for c in XP_CANDIDATES if (mode != 2 or c != 12) and
-                  (c != 18 or w.n // 16 <= SPLIT_MAX_GROUPS) and (c != 21 or w.n // 32 < 512) and
-                  (c != 22 or (w.n % 64 == 0 and w.n // 64 >= 64)) and
-                  # 4-tile split-K: narrow outputs only (few 64-column groups), M > 16
-                  (c != 26 or (m > 16 and w.n % 64 == 0 and w.n // 64 < 256))]
-    if no_split:
-        cands = [c for c in cands if c not in SPLIT_GEMV]
     if not ENABLED or torch.cuda.is_current_stream_capturing():
-        h = heuristic(m, w.n, w.k, mode)
-        return h if h in cands else 1
+        return heuristic(m, w.n, w.k, mode)  # (names only ids that are legal candidates for every key: 1, 5, 6)
+    cands = gemv_candidates(e, m, w.n, mode, x.dtype, xp_in, pack_out, no_split, tiled_packs, w.k)
     def decide():
         pv = _persisted("gemv", key[:-1])
         if pv in cands:

@@ -73,7 +73,8 @@ def test_packaged_tune_table_is_current():
     with open(autotune.PACKAGED_FILE) as f:
         table = json.load(f)
     assert table, "empty packaged table"
-    gemv_ok = {1, 5, 6, 10, 16, 20, autotune.TILED_VARIANT, *autotune.XP_CANDIDATES}
+    gemv_ok = {*autotune.GEMV_VARIANTS, autotune.TILED_VARIANT}
+    assert gemv_ok == {1, 5, 6, 7, 10, 12, 15, 16, 18, 20, 21, 22, 26}
     for key, v in table.items():
         kind, rest = key.split("@", 1)
         assert int(rest.split(":", 1)[0]) == autotune.TUNE_VERSION, key
