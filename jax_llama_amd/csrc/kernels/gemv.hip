@@ -1127,6 +1127,247 @@ int linear_skinny(const void* x, int x_is_f32, const void* W, void* out, int M, 
   return -1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// FP8 (OCP e4m3fn) weight-only linears: W_deq[n, k] = q[n, k] * scale[n], one power-of-two fp32 scale per output row,
+// so W_deq is exact in bf16 and a quantised linear is the bf16 linear on W_deq. The weight is stored in 16(n) x 64(k)
+// blocks [N / 16][K / 64][64 lanes][16 bytes]: lane l of block (nt, kb) holds q[16 nt + (l & 15)][64 kb + 8 (l >> 4)
+// + 0..7] in bytes 0-7 (the element order of the bf16 B fragment of k-step 2 kb) and the same at k + 32 in bytes 8-15
+// (k-step 2 kb + 1): one 16-byte load per lane is 1 KiB per wave, as the bf16 layout, and feeds two MFMAs.
+
+// 8 e4m3 bytes (two dwords) -> the 8 bf16 of one B fragment: four v_cvt_scalef32_pk_bf16_fp8 with scale 1.0 (every
+// e4m3 value is exact in bf16)
+JLA_DEV u32x4 fp8x8_to_bf16(unsigned lo, unsigned hi) {
+  u32x4 r;
+  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
+  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
+  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
+  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
+  return r;
+}
+
+// Dequantise a packed fp8 weight into the bf16 fragment-packed layout (common.h): thread = one lane of one 16 x 64
+// block; reads its 16 bytes, writes its 16 bytes of fragment 2 kb and of 2 kb + 1. q * scale in fp32 then RNE to bf16:
+// exact (a power-of-two scale), so the output is bit-identical to pack_frag16x32(W_deq).
+__global__ void __launch_bounds__(256)
+    dequant_fp8_kernel(const u32x4* __restrict__ W8, const float* __restrict__ scale, u32x4* __restrict__ out,
+                       long long lanes, int KB) {
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= lanes) return;
+  const int lane = (int)(g & 63);
+  const long long blk = g >> 6;  // nt * KB + kb
+  const int nt = (int)(blk / KB);
+  const float s = scale[nt * 16 + (lane & 15)];
+  const u32x4 q = W8[g];
+  const u32x4 f[2] = {fp8x8_to_bf16(q[0], q[1]), fp8x8_to_bf16(q[2], q[3])};
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    float v[8];
+    unpack8(f[h], v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] *= s;
+    out[(2 * blk + h) * 64 + lane] = pack8(v);  // fragment (nt, 2 kb + h) of [N / 16][K / 32][64]
+  }
+}
+
+int dequant_fp8(const void* W8, const float* scale, void* out, int N, int K, hipStream_t s) {
+  if (N <= 0 || K <= 0) return 0;
+  if ((N & 15) || (K & 63)) return -1;
+  const long long lanes = (long long)(N >> 4) * (K >> 6) * 64;
+  const long long grid = (lanes + 255) / 256;
+  if (grid > 0x7fffffffLL) return -1;
+  dequant_fp8_kernel<<<(int)grid, 256, 0, s>>>(static_cast<const u32x4*>(W8), scale, static_cast<u32x4*>(out), lanes,
+                                              K >> 6);
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+// The FP8-weight GEMV body: skinny_body's workgroup (NT n-tiles x the whole K over NW waves, a register ring of U
+// slots, past-the-end refills from the zero fragment) with 64-deep K blocks: wave w takes blocks w, w + NW, ...; one
+// slot is NT weight loads (1 KiB each, non-temporal) plus the x fragments of the block's two k-steps. The weights are
+// converted to bf16 in registers at scale 1.0 and the lane's column scale scale[16 nt + (lane & 15)] multiplies the fp32
+// accumulators before the shared epilogue (the accumulator's lane -> column mapping is the B fragment's; exact for a
+// power of two). ASM: the hand-counted ring of skinny_body (ring.h; tools/check_asm_ring.py checks it at build), built
+// for one and two m-tiles (M <= 32); four m-tiles run compiler-counted loads.
+template <int MT, int NT, int MODE, int NW, int U, bool ASM>
+__global__ void __launch_bounds__(NW * 64)
+    linear_skinny_w8_kernel(const bf16_t* __restrict__ x, const u32x4* __restrict__ W8, const float* __restrict__ scale,
+                            void* __restrict__ out, int M, int N, int K, float eps, int use_rms, int accumulate,
+                            int out_f32, QKVArgs qa) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int KB = K >> 6;
+  const int NTT = N >> 4;
+  const int bx = blockIdx.x;
+  const int nt0 = bx * NT;
+
+  const u32x4* wt[NT];
+  float cs[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int tile = min(nt0 + t, NTT - 1);  // (an odd tile count: the last workgroup re-reads the last tile, not stored)
+    wt[t] = W8 + (size_t)tile * KB * 64 + lane;
+    cs[t] = scale[tile * 16 + (lane & 15)];
+  }
+  const bf16_t* xp[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int row = min(mt * 16 + (lane & 15), M - 1);  // padding rows re-read the last row (not stored)
+    xp[mt] = x + (size_t)row * K + 8 * (lane >> 4);
+  }
+  const u32x4* zfrag = g_zero_frag + lane;
+  const bf16_t* zx = reinterpret_cast<const bf16_t*>(g_zero_frag);
+
+  const int n = (KB - w + NW - 1) / NW;  // 64-deep blocks of this wave: kb = w + i * NW, i < n
+
+  f32x4 acc[MT][NT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float ss[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) ss[mt] = 0.f;
+
+  u32x4 bq[U][NT] = {};
+  XRaw<bf16_t> aq[U][MT][2] = {};
+  constexpr int L = NT + 2 * MT;  // loads per ring slot
+  static_assert(!ASM || L * (U - 1) < 64, "vmcnt range");
+  auto issue = [&](int i, u32x4* b, XRaw<bf16_t>(*a)[2]) {
+    const bool valid = i < n;
+    const size_t kb = (size_t)(w + i * NW);
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+      asm_load_nt<ASM>(b[t], valid ? (const void*)(wt[t] + kb * 64) : (const void*)zfrag);
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      a[mt][0].template load<ASM>(valid ? xp[mt] + kb * 64 : zx);
+      a[mt][1].template load<ASM>(valid ? xp[mt] + kb * 64 + 32 : zx);
+    }
+  };
+  // (as skinny_body: no prologue, the first trip multiplies the zero-initialised slots while it issues blocks 0..U-1)
+  for (int i0 = -U; i0 < n; i0 += U) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if constexpr (ASM) {
+        wait_vmcnt<L * (U - 1)>();  // slot u (the oldest L loads) has landed
+#pragma unroll
+        for (int t = 0; t < NT; ++t) pin(bq[u][t]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          aq[u][mt][0].pin_regs();
+          aq[u][mt][1].pin_regs();
+        }
+      }
+      u32x4 af[MT][2];
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        af[mt][0] = aq[u][mt][0].frag(ss[mt]);
+        af[mt][1] = aq[u][mt][1].frag(ss[mt]);
+      }
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const u32x4 q = bq[u][t];
+        const u32x4 b0 = fp8x8_to_bf16(q[0], q[1]), b1 = fp8x8_to_bf16(q[2], q[3]);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          acc[mt][t] = mfma16x16x32(af[mt][0], b0, acc[mt][t]);
+          acc[mt][t] = mfma16x16x32(af[mt][1], b1, acc[mt][t]);
+        }
+      }
+      issue(i0 + U + u, bq[u], aq[u]);
+    }
+  }
+  if constexpr (ASM) {  // retire the past-the-end refills; every ring register stays live until then (skinny_body)
+    wait_vmcnt<0>();
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) pin(bq[u][t]);
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt) {
+        aq[u][mt][0].pin_regs();
+        aq[u][mt][1].pin_regs();
+      }
+    }
+  }
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[mt][t] *= cs[t];
+
+  skinny_epilogue<MT, NT, MODE, NW, false, false>(acc, ss, 0, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, bx,
+                                                  0, 1);
+}
+
+template <int MT, int NT, int MODE, int NW>
+static int launch_skinny_w8(const void* x, const void* W8, const float* scale, void* out, int M, int N, int K, float eps,
+                            int use_rms, int accumulate, int out_f32, const QKVArgs& qa, hipStream_t s) {
+  // 64-deep blocks in flight per wave: the KiB of weights per wave of launch_skinny's ring (each slot holds twice
+  // its x registers). Hand-counted loads up to two m-tiles: at B = 32 of Llama-3-8B the compiler-counted ring, which
+  // holds fewer loads in flight, measured 4.17 against 3.96 ms per token (profiles/README.md, FP8 weights).
+  constexpr int U0 = (NT == 1) ? 8 : 4;
+  constexpr int U = (U0 / MT) < 2 ? 2 : (U0 / MT);
+  const int NTT = N >> 4;
+  const int grid = (NTT + NT - 1) / NT;
+  const size_t lds = sizeof(float) * (NW * MT * NT * 256 + NW * MT * 16 + MT * 16 + 4);
+  auto kern = &linear_skinny_w8_kernel<MT, NT, MODE, NW, U, (MT <= 2)>;
+  if (lds > 65536) {  // opt in to > 64 KiB of dynamic LDS once (not a stream op: capture-safe)
+    static bool attr_set = false;
+    if (!attr_set) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+  }
+  kern<<<grid, NW * 64, lds, s>>>(static_cast<const bf16_t*>(x), static_cast<const u32x4*>(W8), scale, out, M, N, K, eps,
+                                  use_rms, accumulate, out_f32, qa);
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+// the one form a plan of gemv_w8_plan() names
+template <int MODE>
+static int launch_plan_w8(const void* x, const void* W8, const float* scale, void* out, int M, int N, int K, float eps,
+                          int use_rms, int accumulate, int out_f32, const QKVArgs& qa, const GemvPlan& p,
+                          hipStream_t s) {
+#define JLA_W8(MT, NT, NW)                                                                                            \
+  if (p.mt == MT && p.nt == NT && p.nw == NW)                                                                         \
+  return launch_skinny_w8<MT, NT, MODE, NW>(x, W8, scale, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s)
+  if constexpr (MODE != MODE_SWIGLU) {
+    JLA_W8(1, 1, 4);
+    JLA_W8(2, 1, 8);
+    JLA_W8(4, 1, 8);
+  }
+  if constexpr (MODE != MODE_QKV) {
+    JLA_W8(1, 2, 4);
+    JLA_W8(2, 2, 8);
+    JLA_W8(4, 2, 8);
+  }
+#undef JLA_W8
+  return -1;  // (not a plan of gemv_w8_plan())
+}
+
+int linear_skinny_w8(const void* x, int x_is_f32, const void* W8, const float* scale, void* out, int M, int N, int K,
+                     int mode, float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, hipStream_t s) {
+  const GemvPlanResult r = gemv_w8_plan(M, N, K, mode, x_is_f32 != 0);
+  if (r.rc != 0 || r.plan.mt == 0) return r.rc;
+  if (mode == MODE_QKV && (!qkv || qkv->Dh % 16 || M % qkv->S)) return -1;
+  const int use_rms = rms_eps >= 0.f;
+  const float eps = use_rms ? rms_eps : 0.f;
+  QKVArgs qa{};
+  if (qkv) qa = *qkv;
+  switch (mode) {
+    case MODE_STORE:
+      return launch_plan_w8<MODE_STORE>(x, W8, scale, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, r.plan, s);
+    case MODE_RESIDUAL:
+      return launch_plan_w8<MODE_RESIDUAL>(x, W8, scale, out, M, N, K, eps, use_rms, accumulate, 1, qa, r.plan, s);
+    case MODE_SWIGLU:
+      return launch_plan_w8<MODE_SWIGLU>(x, W8, scale, out, M, N, K, eps, use_rms, accumulate, 0, qa, r.plan, s);
+    case MODE_QKV:
+      return launch_plan_w8<MODE_QKV>(x, W8, scale, out, M, N, K, eps, use_rms, accumulate, 0, qa, r.plan, s);
+  }
+  return -1;
+}
+
 JLA_BOUNDS_ACCESSOR(gemv)
 
 }  // namespace jla

@@ -129,4 +129,23 @@ inline GemvPlanResult gemv_plan(int M, int N, int K, int mode, bool x_f32, bool 
   return {0, "", p};
 }
 
+// The plan of one FP8-weight decode-GEMV call (gemv.hip linear_skinny_w8: e4m3 weights in 16 x 64 blocks, one fp32
+// power-of-two scale per output row). One form per (m-tiles, epilogue): the tiles and waves of the default form above,
+// row-major bf16 x, no K split. Whatever this refuses runs on the bf16 kernels over the dequantised weight.
+inline GemvPlanResult gemv_w8_plan(int M, int N, int K, int mode, bool x_f32) {
+  const auto fail = [](const char* why) { return GemvPlanResult{-1, why, GemvPlan{}}; };
+  if (mode != MODE_STORE && mode != MODE_RESIDUAL && mode != MODE_SWIGLU && mode != MODE_QKV)
+    return fail("the FP8-weight GEMV: store, residual, SwiGLU and qkv epilogues only");
+  if (x_f32) return fail("the FP8-weight GEMV reads bf16 activations");
+  if (M <= 0) return {0, "", GemvPlan{}};
+  if (M > SKINNY_MAX_M || (N & 15) || (K & 63)) return fail("shape: M <= 64, N % 16 == 0, K % 64 == 0");
+  if (mode == MODE_SWIGLU && (N & 31)) return fail("SwiGLU: N % 32 == 0");
+  GemvPlan p{};
+  p.mt = gemv_m_tiles(M);
+  p.nt = mode == MODE_SWIGLU || (mode != MODE_QKV && (N >> 4) >= 2048) ? 2 : 1;
+  p.nw = p.mt == 1 ? 4 : 8;
+  p.ksplit = 1;
+  return {0, "", p};
+}
+
 }  // namespace jla

@@ -77,6 +77,14 @@ int linear_qkv_attn(const bf16_t* x, const void* W, int M, int N, int K, float r
 // id. -3: a split form's slabs (qkv->sk_ws / sk_tk, gemv_split_workspace_floats / gemv_split_tickets) are too small.
 int linear_skinny(const void* x, int x_is_f32, const void* W, void* out, int M, int N, int K, int mode,
                   float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, int variant, hipStream_t s);
+// FP8 (OCP e4m3fn) weight-only linears (gemv.hip): W8 is the weight in 16 x 64 blocks [N / 16][K / 64][64 lanes][16
+// bytes], scale fp32 [N] one power of two per output row (W_deq = q * scale, exact in bf16).
+// dequant_fp8: out = W_deq in the bf16 fragment-packed layout [N / 16][K / 32][64][8] (N % 16 == 0, K % 64 == 0).
+// linear_skinny_w8: the decode GEMV on the fp8 bytes, y = epilogue(x @ W_deq^T), for the calls gemv_w8_plan()
+// (gemv_plan.h) accepts; -1 is its code. qkv as linear_skinny (MODE_QKV's arguments, res_bf16 / pack mirrors).
+int dequant_fp8(const void* W8, const float* scale, void* out, int N, int K, hipStream_t s);
+int linear_skinny_w8(const void* x, int x_is_f32, const void* W8, const float* scale, void* out, int M, int N, int K,
+                     int mode, float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, hipStream_t s);
 int clock_probe(int iters, int grid, unsigned long long* out, hipStream_t s);  // [cycles, 100 MHz ticks]
 // Tiled MFMA GEMM (gemm.hip): y = epilogue(x[M, K] @ W[N, K]^T) on the kernel the tile id names (gemm_plan.h: the
 // tile table, and gemm_plan(), every rule of a legal call; the return codes -1 / -5 / -6 / -7 are its). ksplit > 1

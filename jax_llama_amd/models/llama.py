@@ -34,7 +34,7 @@ from ..parallel.comm import NO_COMM, TPComm
 from ..parallel.partition import shard_tree
 from .kv_cache import KVCache
 from .modules import LLaMABlockCollection
-from .weights import PackedLinear
+from .weights import Fp8Linear, PackedLinear
 
 BF16 = torch.bfloat16
 
@@ -320,6 +320,33 @@ class LLaMAForCausalLM:
         """Reload a ``save_pretrained`` checkpoint (same TP degree) straight into the kernel layout."""
         from ..utils.native_ckpt import from_pretrained
         return from_pretrained(directory, device=device, comm=comm)
+
+    WEIGHT_FORMATS = ("fp8_e4m3",)
+
+    def quantize_weights_(self, fmt: str = "fp8_e4m3") -> "LLaMAForCausalLM":
+        """Replace ``qkv``, ``o``, ``gu`` and ``down`` of every layer by FP8 (OCP e4m3fn) weight-only linears
+        (``models.weights.Fp8Linear``: one power-of-two scale per output row), in place, on either device. Runs after
+        the norm fold and the TP sharding, so each rank quantises its own shard. ``wte``, ``lm_head`` and
+        ``lm_head_f32`` keep their format. The model then computes exactly what a bf16 model loaded with the
+        dequantised weights computes op for op; decode batches up to 64 rows stream the fp8 bytes, larger calls pay
+        one dequant pass per projection. Calling it twice is an error."""
+        if fmt not in self.WEIGHT_FORMATS:
+            raise ValueError(f"quantize_weights_: unknown format {fmt!r} (one of {self.WEIGHT_FORMATS})")
+        if self.weight_format != "bf16":
+            raise RuntimeError(f"quantize_weights_: the weights are already {self.weight_format}")
+        if any(lw.qkv is None for lw in self.layers):
+            raise RuntimeError("quantize_weights_: the model has no weights yet")
+        for lw in self.layers:
+            for name in ("qkv", "o", "gu", "down"):
+                setattr(lw, name, Fp8Linear.from_linear(getattr(lw, name)))
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()
+        return self
+
+    @property
+    def weight_format(self) -> str:
+        """``"bf16"``, or ``"fp8_e4m3"`` after ``quantize_weights_``."""
+        return "fp8_e4m3" if any(getattr(lw.qkv, "fp8", False) for lw in self.layers) else "bf16"
 
     def weight_bytes(self) -> int:
         n = self.wte.numel() * 2 + self.lm_head.nbytes()

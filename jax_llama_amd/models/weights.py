@@ -74,3 +74,67 @@ class PackedLinear:
 
     def nbytes(self) -> int:
         return self.weight.numel() * self.weight.element_size()
+
+
+class Fp8Linear:
+    """FP8 (OCP e4m3fn) weight-only linear with ``PackedLinear``'s surface: ``q [n, k]`` fp8 plus one power-of-two fp32
+    scale per output row (``ops.reference.quantize_fp8_rows``). ``W_deq = q * scale`` is exact in bf16, and the layer is
+    by definition the bf16 linear on ``W_deq`` (``dense()``).
+
+    On the GPU ``qweight`` is the uint8 block layout ``[n/16, k/64, 64, 16]`` (``ops.reference.pack_fp8_16x64``) that the
+    FP8 decode GEMV streams; every other kernel reads the bf16 copy ``ops`` dequantises into a workspace. On the CPU
+    it is the dense fp8 ``[n, k]`` and every op goes through ``dense()``."""
+
+    fp8 = True
+
+    def __init__(self, qweight: torch.Tensor, scale: torch.Tensor, n: int, k: int):
+        self.qweight = qweight
+        self.scale = scale
+        self.n = n
+        self.k = k
+
+    @property
+    def device(self) -> torch.device:
+        return self.qweight.device
+
+    @property
+    def packed(self) -> bool:
+        return self.qweight.dim() == 4
+
+    @classmethod
+    def from_q(cls, q: torch.Tensor, scale: torch.Tensor, device) -> "Fp8Linear":
+        """From the dense fp8 values and their row scales (a checkpoint's tensors)."""
+        n, k = q.shape
+        device = torch.device(device)
+        if n % 16 or k % 64:
+            raise ValueError(f"FP8 linear weights need N%16==0 and K%64==0, got {n}x{k}")
+        if q.dtype != ref.FP8 or scale.numel() != n:
+            raise ValueError(f"Fp8Linear: float8_e4m3fn [N, K] and fp32 [N], got {q.dtype} and {tuple(scale.shape)}")
+        scale = scale.reshape(n).to(device, torch.float32).contiguous()
+        if device.type == "cuda":
+            return cls(ref.pack_fp8_16x64(q.contiguous()).to(device), scale, n, k)
+        return cls(q.to(device).contiguous(), scale, n, k)
+
+    @classmethod
+    def from_dense(cls, w: torch.Tensor, device, fold: Optional[torch.Tensor] = None) -> "Fp8Linear":
+        """Quantise a ``[n, k]`` weight (after the optional norm fold and its bf16 rounding, as ``PackedLinear``)."""
+        src = w if fold is None else w.float() * fold.to(w.device).float()[None, :]
+        q, scale = ref.quantize_fp8_rows(src.to(BF16))
+        return cls.from_q(q, scale, device)
+
+    @classmethod
+    def from_linear(cls, lin: PackedLinear) -> "Fp8Linear":
+        return cls.from_dense(lin.dense(), lin.device)
+
+    def q(self) -> torch.Tensor:
+        """The dense ``[n, k]`` fp8 values."""
+        if self.packed:
+            return ref.unpack_fp8_16x64(self.qweight, self.n, self.k)
+        return self.qweight
+
+    def dense(self) -> torch.Tensor:
+        """``W_deq`` as the ``[n, k]`` bf16 matrix."""
+        return ref.dequantize_fp8_rows(self.q(), self.scale)
+
+    def nbytes(self) -> int:
+        return self.n * self.k + 4 * self.n

@@ -250,11 +250,50 @@ def packed_empty(m: int, cols: int, device) -> torch.Tensor:
     return torch.empty(packed_rows(m), cols, dtype=BF16, device=device)
 
 
+# ---- FP8 (e4m3) weight-only linears (models.weights.Fp8Linear; csrc/kernels/gemv.hip). Decode rows (M <= 64, bf16 x)
+# run the FP8 GEMV on the fp8 bytes (``_w8_fast``: the one rule is gemv_w8_plan() of csrc/kernels/gemv_plan.h, and the
+# tuner is never asked). Every other call first dequantises the weight into a bf16 workspace (``bf16_weight``) and
+# runs the existing bf16 kernel on it unchanged: W_deq is exact in bf16, so that is the same kernel on the same bits
+# as a PackedLinear of W_deq, plus one dequant pass per call.
+class _Dequantized:
+    """What the bf16 kernels read of an Fp8Linear: ``weight`` (fragment-packed bf16 workspace), ``n``, ``k``."""
+
+    def __init__(self, weight, n, k):
+        self.weight, self.n, self.k = weight, n, k
+
+
+def is_fp8(w) -> bool:
+    return bool(getattr(w, "fp8", False))
+
+
+def bf16_weight(w):
+    """The weight the bf16 kernels read. A ``PackedLinear``: itself (no kernel, launch or allocation added). An
+    ``Fp8Linear``: ``W_deq`` dequantised (``dequant_fp8``) into the workspace keyed by its shape, so two weights one
+    launch reads never share a buffer; sized in the eager warm-up step like every workspace (nothing allocates under
+    graph capture)."""
+    if not is_fp8(w):
+        return w
+    buf = workspace.get(f"w8_deq_{w.n}x{w.k}", w.n * w.k, BF16, w.device).view(w.n // 16, w.k // 32, 64, 8)
+    ext().dequant_fp8(w.qweight, w.scale, w.n, w.k, buf)
+    return _Dequantized(buf, w.n, w.k)
+
+
+def _w8_fast(e, x, w, mode) -> bool:
+    """Whether this call on an ``Fp8Linear`` runs the FP8 decode GEMV (else the dequant path)."""
+    return x.shape[0] > 0 and e.gemv_w8_plan_check(x.shape[0], w.n, w.k, mode, x.dtype != BF16)[0] == 0
+
+
 def _gpu_linear(x, w, out, mode, rms_eps, accumulate, mirror=None, x_packed=None, pack_out=None):
     assert x.is_contiguous() and out.is_contiguous()
     assert x.shape[1] == w.k, (x.shape, w.k)
     m = x.shape[0]
     e = ext()
+    if is_fp8(w):
+        if _w8_fast(e, x, w, mode):
+            e.linear_skinny_w8(x, w.qweight, w.scale, w.n, w.k, out, mode, -1.0 if rms_eps is None else float(rms_eps),
+                               bool(accumulate), mirror, pack_out if mode != MODE_STORE else None)
+            return
+        w = bf16_weight(w)
     if m > e.SKINNY_MAX_M:
         x_packed = pack_out = None
     v = TILED if m > e.SKINNY_MAX_M else _variant(e, x, w, mode, x_packed, pack_out)
@@ -452,6 +491,14 @@ def linear_qkv_rope(x: torch.Tensor, w, rms_eps: Optional[float], table: torch.T
                                    n_heads, n_kv_heads, head_dim)
     m = x.shape[0]
     e = ext()
+    if is_fp8(w):
+        if _w8_fast(e, x, w, MODE_QKV):
+            q = torch.empty(m, n_heads, head_dim, dtype=BF16, device=x.device)
+            e.linear_qkv_w8(x, w.qweight, w.scale, w.n, w.k, -1.0 if rms_eps is None else float(rms_eps), table,
+                            positions.reshape(-1).to(torch.int32), k_cache, v_cache, _slot_tensor(slot0, x.device),
+                            int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q)
+            return q
+        w = bf16_weight(w)
     if m > e.SKINNY_MAX_M:
         x_packed = None
     v = TILED if m > e.SKINNY_MAX_M else _variant(e, x, w, MODE_QKV, x_packed)
@@ -537,7 +584,7 @@ def _num_cus(device) -> int:
 def qkv_attention_o_groups(x: torch.Tensor, w_o, n_heads: int, n_kv_heads: int) -> int:
     """Workgroups of the o projection when the fused decode launch can also run it (``linear_qkv_attention(o=...)``),
     else 0."""
-    if not QKV_ATTN_O or not _is_gpu(x):
+    if not QKV_ATTN_O or not _is_gpu(x) or is_fp8(w_o):
         return 0
     return int(ext().qkv_attn_o_groups(x.shape[0], n_heads // n_kv_heads, w_o.n, w_o.k))
 
@@ -547,8 +594,8 @@ def qkv_attention_splits(x: torch.Tensor, w, k_cache: torch.Tensor, seq_len: int
     """Attention workgroups per (row, kv head) pair of the fused qkv + attention launch for this decode step, or 0
     when it does not apply (prefill, a key mask, M > 32, a cache longer than 512, or a grid the CUs cannot hold at
     once). ``o_groups``: the launch also holds the o projection's workgroups (``qkv_attention_o_groups``)."""
-    if not QKV_ATTN or seq_len != 1 or key_mask is not None or not _is_gpu(x) or x.dtype != BF16:
-        return 0
+    if not QKV_ATTN or seq_len != 1 or key_mask is not None or not _is_gpu(x) or x.dtype != BF16 or is_fp8(w):
+        return 0  # (an Fp8Linear: the fused launch reads bf16 fragments only)
     m = x.shape[0]
     if QKV_ATTN == 1 and (m > 4 or n_heads < 8 * n_kv_heads):
         return 0
@@ -674,6 +721,7 @@ def linear_argmax(x: torch.Tensor, w, rms_eps: Optional[float] = None):
     m = x.shape[0]
     if not _is_gpu(x):
         return argmax(linear(x, w, rms_eps, out_dtype=torch.float32))
+    w = bf16_weight(w)
     if m <= ext().SKINNY_MAX_M and SKINNY_ARGMAX:
         e = ext()
         v = _variant(e, x, w, MODE_STORE, no_split=True)  # the logits GEMV's main loop: its tuned variant applies
@@ -738,6 +786,7 @@ def linear_logprob(x: torch.Tensor, w, targets: torch.Tensor, rms_eps: Optional[
     ``logprob_fused``; else ``linear`` + ``logprob`` over row chunks of at most LOGPROB_CHUNK_BYTES of logits."""
     if not _is_gpu(x):
         return ref.linear_logprob(x, w.dense(), targets, rms_eps, col_offset)
+    w = bf16_weight(w)
     m = x.shape[0]
     assert x.is_contiguous() and x.shape[1] == w.k, (x.shape, w.k)
     tg = targets.reshape(-1).to(torch.int32)

@@ -60,6 +60,65 @@ def unpack_frag16x32(p: torch.Tensor, n: int, k: int) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------
+# FP8 (OCP e4m3fn) weight-only quantisation: one power-of-two scale per output row
+# ----------------------------------------------------------------------------------
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+FP8_EXP_CLAMP = 100
+
+
+def quantize_fp8_rows(w: torch.Tensor):
+    """``[N, K]`` weight -> ``(q float8_e4m3fn [N, K], scale fp32 [N])`` with ``scale[n] = 2^e[n]``,
+    ``e[n] = ceil(log2(amax_n / 448))`` clamped to [-100, 100] (0 for an all-zero row) and ``q = fp8_rne(w / scale)``.
+    The scale is a power of two, so ``dequantize_fp8_rows`` (``q * scale``) is exact in bf16.
+
+    The exponent comes from ``frexp`` (no rounded logarithm): ``amax = m 2^x`` with ``m`` in [0.5, 1) and
+    ``448 = 0.875 * 2^9``, so ``e = x - 9`` where ``m <= 0.875`` and ``x - 8`` above."""
+    if w.dim() != 2:
+        raise ValueError(f"quantize_fp8_rows: a [N, K] matrix, got {tuple(w.shape)}")
+    wf = w.float()
+    amax = wf.abs().amax(1)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.875, x - 9, x - 8)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).clamp(-FP8_EXP_CLAMP, FP8_EXP_CLAMP)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    q = (wf / scale[:, None]).clamp(-FP8_MAX, FP8_MAX).to(FP8)  # (the clamp acts only where e was clamped)
+    return q, scale
+
+
+def dequantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``W_deq = q * scale`` as bf16 (exact)."""
+    return (q.float() * scale.float()[:, None]).to(BF16)
+
+
+def _check_fp8_shape(n: int, k: int):
+    if n <= 0 or k <= 0 or n % 16 or k % 64:
+        raise ValueError(f"FP8 linear weights need N % 16 == 0 and K % 64 == 0, got {n}x{k}")
+
+
+def pack_fp8_16x64(q: torch.Tensor) -> torch.Tensor:
+    """``[N, K]`` float8 (or its uint8 bytes) -> uint8 ``[N/16, K/64, 64 lanes, 16 bytes]``: lane ``l`` of block
+    ``(nt, kb)`` holds ``q[16 nt + (l & 15), 64 kb + 8 (l >> 4) + 0..7]`` in bytes 0-7 (the element order of the bf16
+    fragment of k-step ``2 kb``, ``pack_frag16x32``) and the same at ``k + 32`` in bytes 8-15 (k-step ``2 kb + 1``)."""
+    if q.dim() != 2:
+        raise ValueError(f"pack_fp8_16x64: a [N, K] matrix, got {tuple(q.shape)}")
+    n, k = q.shape
+    _check_fp8_shape(n, k)
+    b = q if q.dtype == torch.uint8 else q.view(torch.uint8)
+    return (b.reshape(n // 16, 16, k // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous()
+            .reshape(n // 16, k // 64, 64, 16))
+
+
+def unpack_fp8_16x64(p: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """Inverse of ``pack_fp8_16x64``: the ``[n, k]`` float8 matrix."""
+    _check_fp8_shape(n, k)
+    if p.dtype != torch.uint8 or p.numel() != n * k:
+        raise ValueError(f"unpack_fp8_16x64: uint8 with {n * k} bytes, got {p.dtype} {tuple(p.shape)}")
+    return (p.reshape(n // 16, k // 64, 4, 16, 2, 8).permute(0, 3, 1, 4, 2, 5).contiguous()
+            .reshape(n, k).view(FP8))
+
+
+# ----------------------------------------------------------------------------------
 # Elementwise / normalisation
 # ----------------------------------------------------------------------------------
 def embedding(ids: torch.Tensor, table: torch.Tensor) -> torch.Tensor:

@@ -7,7 +7,7 @@ which for 65B/70B takes minutes. ``save_pretrained`` writes what the kernels act
 ``from_pretrained`` is one mmap + host-to-device copy per tensor:
 
     <dir>/config.json                      LLaMAConfig (HF-style)
-    <dir>/jla_native.json                  {"format": 1, "tp": N, "norm_folded": true}
+    <dir>/jla_native.json                  {"format": 1, "tp": N, "norm_folded": true[, "weights": "fp8_e4m3"]}
     <dir>/model-rank{r:02d}-of-{N:02d}.safetensors
 
 Tensors per rank (bf16 unless noted; ``[n, k]`` = Meta ``[out, in]`` orientation, this rank's
@@ -17,6 +17,10 @@ shard, RMSNorm gains already folded into ``qkv``/``gate_up``/``lm_head`` columns
     h.{i}.qkv [(H+2Hkv)/tp*Dh, D]  h.{i}.o [D, H/tp*Dh]
     h.{i}.gate_up [2F/tp, D] (w1/w3 interleaved in 16-row tiles)   h.{i}.down [D, F/tp]
     h.{i}.attention_norm [D] fp32   h.{i}.ffn_norm [D] fp32        lm_head [V/tp, D]
+
+A model after ``quantize_weights_("fp8_e4m3")`` stores, for each of ``qkv`` / ``o`` / ``gate_up`` / ``down``, the fp8
+bytes ``h.{i}.<name>.q`` (uint8 ``[n, k]``) and the row scales ``h.{i}.<name>.scale`` (fp32 ``[n]``) instead, and marks
+``"weights": "fp8_e4m3"`` in ``jla_native.json``; the reload is exact (same bytes, same scales).
 
 Dense ``[n, k]`` is stored (not the MFMA fragment packing), so files are device-independent and the
 reload into the packed GPU layout is exact (bit-for-bit the same weights). Reloading needs the
@@ -45,12 +49,15 @@ def save_pretrained(model, directory: str) -> str:
 
     os.makedirs(directory, exist_ok=True)
     rank, size = model.tp_rank, model.tp_size
+    fp8 = model.weight_format == "fp8_e4m3"
     t = {"wte": model.wte, "ln_f": model.ln_f.float(), "lm_head": model.lm_head.dense()}
     for i, lw in enumerate(model.layers):
-        t[f"h.{i}.qkv"] = lw.qkv.dense()
-        t[f"h.{i}.o"] = lw.o.dense()
-        t[f"h.{i}.gate_up"] = lw.gu.dense()
-        t[f"h.{i}.down"] = lw.down.dense()
+        for name, lin in (("qkv", lw.qkv), ("o", lw.o), ("gate_up", lw.gu), ("down", lw.down)):
+            if fp8:  # the fp8 bytes (safetensors stores them as uint8) and the row scales: the reload is exact
+                t[f"h.{i}.{name}.q"] = lin.q().view(torch.uint8)
+                t[f"h.{i}.{name}.scale"] = lin.scale
+            else:
+                t[f"h.{i}.{name}"] = lin.dense()
         t[f"h.{i}.attention_norm"] = lw.attention_norm.float()
         t[f"h.{i}.ffn_norm"] = lw.ffn_norm.float()
     t = {k: v.detach().to("cpu").contiguous() for k, v in t.items()}
@@ -59,8 +66,11 @@ def save_pretrained(model, directory: str) -> str:
     if rank == 0:
         model.config.save_pretrained(directory)
         with open(os.path.join(directory, "jla_native.json"), "w") as f:
-            json.dump({"format": FORMAT, "tp": size, "norm_folded": True,
-                       "num_hidden_layers": model.config.num_hidden_layers}, f)
+            meta = {"format": FORMAT, "tp": size, "norm_folded": True,
+                    "num_hidden_layers": model.config.num_hidden_layers}
+            if fp8:  # (a bf16 checkpoint's metadata is what it always was)
+                meta["weights"] = "fp8_e4m3"
+            json.dump(meta, f)
     return path
 
 
@@ -69,12 +79,15 @@ def from_pretrained(directory: str, device="cpu", comm=None, config: Optional[LL
     from safetensors import safe_open
 
     from ..models.llama import LLaMAForCausalLM
-    from ..models.weights import PackedLinear
+    from ..models.weights import Fp8Linear, PackedLinear
 
     with open(os.path.join(directory, "jla_native.json")) as f:
         meta = json.load(f)
     if meta.get("format") != FORMAT:
         raise ValueError(f"unsupported native checkpoint format {meta.get('format')}")
+    fp8 = meta.get("weights", "bf16") == "fp8_e4m3"
+    if not fp8 and meta.get("weights", "bf16") != "bf16":
+        raise ValueError(f"unsupported native checkpoint weight format {meta.get('weights')!r}")
     cfg = config or LLaMAConfig.from_pretrained(directory)
     model = LLaMAForCausalLM(cfg, device=device, comm=comm, _do_init=False)
     if meta["tp"] != model.tp_size:
@@ -86,14 +99,17 @@ def from_pretrained(directory: str, device="cpu", comm=None, config: Optional[LL
             x = f.get_tensor(name)
             return x.to(dev, dtype) if dtype is not None else x.to(dev)
 
+        def lin(name):
+            if fp8:
+                return Fp8Linear.from_q(f.get_tensor(name + ".q").view(torch.float8_e4m3fn),
+                                        f.get_tensor(name + ".scale"), dev)
+            return PackedLinear.from_dense(f.get_tensor(name), dev)
+
         model.wte = get("wte", torch.bfloat16).contiguous()
         model.ln_f = get("ln_f", torch.float32)
         model.lm_head = PackedLinear.from_dense(f.get_tensor("lm_head"), dev)
         for i, lw in enumerate(model.layers):
-            lw.qkv = PackedLinear.from_dense(f.get_tensor(f"h.{i}.qkv"), dev)
-            lw.o = PackedLinear.from_dense(f.get_tensor(f"h.{i}.o"), dev)
-            lw.gu = PackedLinear.from_dense(f.get_tensor(f"h.{i}.gate_up"), dev)
-            lw.down = PackedLinear.from_dense(f.get_tensor(f"h.{i}.down"), dev)
+            lw.qkv, lw.o, lw.gu, lw.down = (lin(f"h.{i}.{name}") for name in ("qkv", "o", "gate_up", "down"))
             lw.attention_norm = get(f"h.{i}.attention_norm", torch.float32)
             lw.ffn_norm = get(f"h.{i}.ffn_norm", torch.float32)
     return model

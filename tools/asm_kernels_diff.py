@@ -17,7 +17,9 @@ def kernels(path):
         start = text.index(f"\n{name}:", 0) + 1
         end = text.index(".end_amdhsa_kernel", m.end())
         assert start < m.start() and name not in out, name
-        out[name] = re.sub(r"\bL?BB\d+_", "BB_", text[start:end])  # (labels, and the loop comments that name them)
+        body = re.sub(r"\bL?BB\d+_", "BB_", text[start:end])  # (labels, and the loop comments that name them)
+        # (a label's loop comment is padded to a column: the padding changes with the digits of the masked index)
+        out[name] = re.sub(r"(?m)^(\.BB_\d+:)[ \t]+;", r"\1 ;", body)
     return out
 
 

@@ -24,6 +24,10 @@ def main():
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--tp-proxy", type=int, default=1, help="> 1: ONE rank of that MP degree on this GPU "
                     "(parallel/comm.py TPRankProxyComm; bench.py tp_rank_proxy)")
+    ap.add_argument("--weights", nargs="+", choices=["bf16", "fp8"], default=["bf16"],
+                    help="fp8: the layer projections quantised to FP8 e4m3 (LLaMAForCausalLM.quantize_weights_); "
+                    "`bf16 fp8`: one model of each in this process, measured alternately per point")
+    ap.add_argument("--reps", type=int, default=1, help="repeats of every point (alternating over --weights)")
     ap.add_argument("--tune-report", action="store_true", help="print the decode-kernel choices and the graph-timed "
                     "microseconds of every candidate measured (ops/autotune.py)")
     args = ap.parse_args()
@@ -36,15 +40,23 @@ def main():
     if args.tp_proxy > 1:
         from jax_llama_amd.parallel import TPRankProxyComm
         comm = TPRankProxyComm.create(args.tp_proxy, fused_hidden=cfg.hidden_size)
-    m = LLaMAForCausalLM(cfg, device="cuda", comm=comm, _do_init=False).init_random(seed=1)
+    models = {}
+    for wf in args.weights:
+        models[wf] = LLaMAForCausalLM(cfg, device="cuda", comm=comm, _do_init=False).init_random(seed=1)
+        if wf == "fp8":
+            models[wf].quantize_weights_("fp8_e4m3")
     for b in args.batch:
-        r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample)
-        r["model"] = args.model
-        r["mp"] = args.tp_proxy
-        r["fused_row_parallel"] = comm is not None and comm.fused is not None
-        r["hbm_roofline_ms"] = round(m.streamed_weight_bytes_per_token() / 6.29e12 * 1e3, 4)
-        print(json.dumps(r), flush=True)
-        torch.cuda.empty_cache()
+        for rep in range(args.reps):
+            for wf, m in models.items():
+                r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample)
+                r["model"] = args.model
+                r["mp"] = args.tp_proxy
+                r["weights"] = wf
+                r["rep"] = rep
+                r["fused_row_parallel"] = comm is not None and comm.fused is not None
+                r["hbm_roofline_ms"] = round(m.streamed_weight_bytes_per_token() / 6.29e12 * 1e3, 4)
+                print(json.dumps(r), flush=True)
+                torch.cuda.empty_cache()
     if args.tune_report:
         from jax_llama_amd.ops import autotune
         for (m, n, k, _), t in autotune.measured().items():
