@@ -547,8 +547,15 @@ void attn_decode(Tensor q, Tensor kc, Tensor vc, Tensor slot, Tensor kv_start, c
   check(t_cap <= T, "t_cap exceeds the cache length");
   check_gpu(ws, "ws");
   check_gpu(tickets, "tickets");
-  check(ws.scalar_type() == torch::kFloat32 && ws.numel() >= b * h * nsplit * (dh + 2), "workspace too small");
-  check(tickets.scalar_type() == torch::kInt32 && tickets.numel() >= b * hkv, "tickets too small");
+  // the one resolver (kernels/attn_plan.h) says whether the shape is served and what the launch needs
+  const jla::AttnPlanResult r = jla::attn_decode_plan(jla::attn_knobs(), b, h, hkv, dh, t_cap, key_mask.has_value());
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: attn_decode: no plan (", r.why, "; see attn_plan.h)");
+  TORCH_CHECK(nsplit == r.plan.nsplit, "jax_llama_amd._C: attn_decode: nsplit ", nsplit, " is not the plan's ",
+              r.plan.nsplit, " (attn_decode_plan_check)");
+  check(!out_pack.has_value() || r.plan.packs,
+        "attn_decode: this launch does not write the packed copy (attn_decode_plan_check's packs)");
+  check(ws.scalar_type() == torch::kFloat32 && (size_t)ws.numel() >= r.plan.ws_floats, "workspace too small");
+  check(tickets.scalar_type() == torch::kInt32 && tickets.numel() >= r.plan.tickets, "tickets too small");
   const uint8_t* km = key_mask.has_value() ? ptr<uint8_t>(*key_mask) : nullptr;
   const int ml = key_mask.has_value() ? key_mask->size(1) : 0;
   rc(jla::attn_decode(cbf(q), cbf(kc), cbf(vc), ptr<int32_t>(slot), ptr<int32_t>(kv_start), km, ml, bf(out),
@@ -936,8 +943,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("rope_kv_write", &rope_kv_write);
   m.def("attn_set_impl", [](int64_t impl, int64_t waves_target) { jla::attn_set_impl(impl, waves_target); },
         py::arg("impl"), py::arg("waves_target") = 0);
-  m.def("attn_decode_splits",
-        [](int64_t b, int64_t hkv, int64_t t, int64_t rep) { return jla::attn_decode_splits(b, hkv, t, rep); });
+  m.def("attn_reset_knobs", []() { jla::attn_reset_knobs(); }, "every attn_set_* knob back to its default");
+  // (rc, why, kernel, nsplit, packs, ws_floats, tickets, rep, kpg, ring, fold, wpp, split_len) of the decode-attention
+  // launch for this shape under the current knobs (kernels/attn_plan.h)
+  m.def("attn_decode_plan_check", [](int64_t b, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap, bool masked) {
+    const jla::AttnPlanResult r =
+        jla::attn_decode_plan(jla::attn_knobs(), (int)b, (int)h, (int)hkv, (int)dh, (int)t_cap, masked);
+    const jla::AttnPlan& p = r.plan;
+    return py::make_tuple(r.rc, r.why, r.rc ? "" : jla::attn_kernel_name(p.kernel), p.nsplit, p.packs,
+                          (int64_t)p.ws_floats, p.tickets, p.rep, p.kpg, p.ring, p.fold, p.wpp, p.split_len);
+  }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"));
+  // the two older queries, now of the same plan (no key mask; packs does not depend on t_cap)
+  m.def("attn_decode_splits", [](int64_t b, int64_t hkv, int64_t t, int64_t rep) {
+    return jla::attn_decode_plan(jla::attn_knobs(), (int)b, (int)(hkv * rep), (int)hkv, jla::ATTN_DH, (int)t, false)
+        .plan.nsplit;
+  });
+  m.def("attn_decode_packs", [](int64_t b, int64_t hkv, int64_t rep) {
+    return (int)jla::attn_decode_plan(jla::attn_knobs(), (int)b, (int)(hkv * rep), (int)hkv, jla::ATTN_DH, 1, false)
+        .plan.packs;
+  });
   m.def("linear_qkv", &linear_qkv, py::arg("x"), py::arg("w"), py::arg("n"), py::arg("k"), py::arg("rms_eps"),
         py::arg("table"), py::arg("positions"), py::arg("kc"), py::arg("vc"), py::arg("slot"), py::arg("seq_len"),
         py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("q"), py::arg("variant"), py::arg("ws"), py::arg("tickets"),
@@ -972,7 +996,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("qkv_attn_occupancy", [](int64_t m, int64_t rep, int64_t spl, int64_t o_groups) {
     return jla::qkv_attn_occupancy((int)m, (int)rep, (int)spl, (int)o_groups);
   }, py::arg("m"), py::arg("rep"), py::arg("spl") = 1, py::arg("o_groups") = 0);
-  m.def("attn_decode_packs", &jla::attn_decode_packs);
   m.def("skinny_workspace", &skinny_workspace);
   m.def("linear_skinny_argmax", &linear_skinny_argmax);
   m.def("gemm_tp_residual", &gemm_tp_residual, py::arg("state"), py::arg("x"), py::arg("w"), py::arg("n"), py::arg("k"),
@@ -1032,7 +1055,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("attn_set_v6", [](int64_t mode) { jla::attn_set_v6((int)mode); });
   m.def("attn_set_v6_wpp", [](int64_t wpp) { jla::attn_set_v6_wpp((int)wpp); });
   m.def("attn_set_v6_diag", [](int64_t d) { jla::attn_set_v6_diag((int)d); });
-  m.def("attn_v6_wpp", [](int64_t pairs) { return jla::attn_v6_wpp((int)pairs); });
   m.def("attn_decode", &attn_decode, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("slot"),
         py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"), py::arg("ws"), py::arg("tickets"), py::arg("t_cap"),
         py::arg("nsplit"), py::arg("out_pack") = py::none());

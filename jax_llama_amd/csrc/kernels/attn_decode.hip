@@ -6,23 +6,19 @@
 // share a kv head are processed together so K/V are read from HBM once), and only keys
 // [kv_start, slot] are touched (the reference attends over the whole cache length).
 //
-// One kernel per regime (attn_decode below picks by (row, kv head) pairs and query heads per kv head, REP):
-//   v5  split small batch, <= 64 pairs (<= 256 at REP >= 8)   -- the latency-bound B = 1..8 steps
-//   v6  matrix-core scores / P.V, REP >= 8 and 8..2047 pairs  -- the 70B tensor-parallel shard (attn_decode_mma.hip)
-//   v3  one workgroup per pair, up to 4096 pairs (REP <= 8)    -- mid batches
-//   v4  one wave per pair, register ring, one split, no key mask -- large batches (the B = 2048 headline)
-//   v2  one wave per (pair, key split), LDS ring, optional key mask -- large batches with a padding mask, and the
-//       fallback for every other shape (REP 16 mid batches)
+// Five kernels (v2 .. v6: v6 is attn_decode_mma.hip); which one serves a launch, and with what geometry, is decided by
+// attn_decode_plan() (attn_plan.h), and attn_decode() at the end of this file launches what the plan names.
 // With splits, each split publishes (m, l, o[Dh]) with write-through stores and bumps a per-pair ticket; the last
 // arriver merges the splits (log-sum-exp), so decode attention is ONE launch (cdna_hip_programming.md Guideline 16,
 // sc1-store / sc1-load form; the last arriver resets the ticket for the next replay).
 // Rows with no valid key produce 0 (never NaN: -inf maxima are guarded).
+#include "attn_plan.h"
 #include "common.h"
 #include "launchers.h"
 
 namespace jla {
 
-constexpr int AD_DH = 128;
+constexpr int AD_DH = ATTN_DH;
 constexpr int AD_WAVES = 4;
 
 JLA_DEV void st_wt(float* p, float v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -198,14 +194,7 @@ __global__ void __launch_bounds__(AD3_WAVES * 64)
 // projection). Splits outside the valid key range exit at once (the grid covers the whole cache, the valid range is
 // device state), so the ticket counts only the active splits; a pair with one active split writes directly.
 constexpr int AD5_WAVES = 4;
-// splits the last arriver merges per round (all of a round's partial loads in flight together): 4 or 12; by default
-// 12 from 16 (row, kv head) pairs on (70B MP 8 B = 32 T = 384: 13.9 -> 12.8 us) and 4 below (B = 1: 8.8 vs 9.4 us;
-// profiles/r3_attn_decode_v5_fold_ab.jsonl). attn_set_v5_fold(4 / 12) pins one (A/B), 0 = by pairs.
-static int g_attn_v5_fold = 0;
-void attn_set_v5_fold(int n) { g_attn_v5_fold = (n == 4 || n == 12) ? n : 0; }
-static int g_attn_v5_max_pairs = 64;  // v5 up to this many (row, kv head) pairs (0: off)
-void attn_set_v5_max_pairs(int n) { g_attn_v5_max_pairs = n < 0 ? 64 : n; }
-static int kpg5(int rep) { return rep >= 16 ? 1 : (rep == 8 ? 2 : (rep == 4 ? 4 : 8)); }
+// AD5_FOLD: splits the last arriver merges per round (all of a round's partial loads in flight together), 4 or 12
 
 template <int REP, int KPG, int AD5_FOLD>
 __global__ void __launch_bounds__(AD5_WAVES * 64)
@@ -419,14 +408,8 @@ __global__ void __launch_bounds__(AD5_WAVES * 64)
 // the lane holds dims [8*li, 8*li + 8) of it, so one wave load instruction covers 4 consecutive
 // cache rows (1 KiB contiguous). QK^T: 8 FMAs + a 16-lane DPP sum; P.V: lane-local over the group's
 // rows, summed across the 4 groups once per item.
-static int g_attn_waves_target = 2048;
-static int g_attn_v2_min_pairs = 4096;
 static int g_attn_diag = 0;  // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)
-// register-ring streaming kernel (v4) for one-split large batches without a key mask: 5-12 % faster than v2 at
-// B = 512-2048 (profiles/r2_attn_decode_v4_vs_v2.jsonl); impl 2 (default) uses it, impl 4 pins v2 (KPG 4, 2 slots)
-static bool g_attn_v4 = true;
 void attn_set_diag(int d) { g_attn_diag = d; }
-void attn_set_impl(int impl, int waves_target);
 
 template <int REP, int KPG, int NS, bool MASK>
 __global__ void __launch_bounds__(64)
@@ -830,195 +813,112 @@ __global__ void __launch_bounds__(64)
   }
 }
 
-static int g_kpg_small = 8;  // v2 ring geometry for REP <= 4 below 16384 pairs (impl 4: 4)
-// the geometry by size: at >= 16384 (row, kv head) pairs (B >= 2048 at 8 kv heads) the 17-KiB (KPG 4, 2 slots) ring --
-// 9 waves per CU instead of 4 -- streams 5.4-5.8 TB/s against 4.0-5.6 for (KPG 8, 2 slots), which stays best at
-// B = 1024 (profiles/r2_attn_decode_b2048_geometry.jsonl)
-static bool g_geo_auto = true;
-static int kpg_v2(int rep, int pairs) {
-  if (rep <= 4) return (g_geo_auto && pairs >= 16384) ? 4 : g_kpg_small;
-  return rep == 8 ? 2 : 1;
-}
-
+// The process-wide knobs of the dispatch (attn_plan.h AttnKnobs: what each one means, and the defaults). The setters are
+// for tests and tools (A/B runs); attn_reset_knobs() restores every default.
+static AttnKnobs g_attn_knobs;
+const AttnKnobs& attn_knobs() { return g_attn_knobs; }
+void attn_reset_knobs() { g_attn_knobs = AttnKnobs{}; }
 // impl 2 = default dispatch; 4 = v2 with the (KPG 4, 2 slots) ring and no v4 (tests / A/B).
-// waves_target > 0: v2's split count target; < 0: v2 (or v4) down to -waves_target pairs
+// waves_target > 0: v2's split count target; < 0: v2 (or v4) down to -waves_target pairs; 0: the default v2 threshold
+// (and the waves target as it is)
 void attn_set_impl(int impl, int waves_target) {
-  g_kpg_small = impl == 4 ? 4 : 8;
-  g_geo_auto = impl != 4;
-  g_attn_v4 = impl != 4;
-  if (waves_target > 0) g_attn_waves_target = waves_target;
-  g_attn_v2_min_pairs = waves_target < 0 ? -waves_target : 4096;  // < 0: force v2 down to -target pairs
+  g_attn_knobs.v2_kpg4 = impl == 4;
+  g_attn_knobs.v4 = impl != 4;
+  if (waves_target > 0) g_attn_knobs.waves_target = waves_target;
+  g_attn_knobs.v2_min_pairs = waves_target < 0 ? -waves_target : ATTN_V2_MIN_PAIRS;
 }
+void attn_set_v3_max_pairs(int n) { g_attn_knobs.v3_max_pairs = n; }
+void attn_set_v3_kpg(int mult) { g_attn_knobs.v3_kpg_mult = mult >= 4 ? 4 : (mult >= 2 ? 2 : (mult == 1 ? 1 : 0)); }
+void attn_set_v5_max_pairs(int n) { g_attn_knobs.v5_max_pairs = n < 0 ? AttnKnobs{}.v5_max_pairs : n; }
+void attn_set_v5_fold(int n) { g_attn_knobs.v5_fold = (n == 4 || n == 12) ? n : 0; }
+void attn_set_v6(int mode) { g_attn_knobs.v6_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
+void attn_set_v6_wpp(int wpp) { g_attn_knobs.v6_wpp = (wpp == 1 || wpp == 2 || wpp == 4 || wpp == 8) ? wpp : 0; }
 
-// v2 streams whole (b, kv head) pairs from ~4096 pairs (B = 512 at 8 kv heads) up.
-// The one-split register-ring stream (v4) also serves batches above the decode GEMV's rows (B > 64) below the v2
-// threshold: at rep <= 4 from there on, at rep 8 from 2048 (row, kv head) pairs. Graph-timed with cold K/V
-// (profiles/r3_attn_decode_v4_midbatch.jsonl): Llama-3-8B B = 128 / 256 (T 384) 71.9 / 129 us (v3) -> 57.9 / 70.5;
-// Llama-3-70B B = 256 (T 256 / 384) 158 / 206 -> 87 / 125; v3 stays ahead at B <= 64 (where it also writes the
-// packed copy the o projection's GEMV reads) and at rep 8 below 2048 pairs.
-static bool v4_midbatch(int B, int Hkv, int rep) {
-  return g_attn_v4 && g_attn_v2_min_pairs == 4096 && rep <= 8 &&
-         ((rep <= 4 && B > 32) || (rep == 8 && B * Hkv >= 2048));
-}
-static bool use_v2(int B, int Hkv, int rep) { return B * Hkv >= g_attn_v2_min_pairs || v4_midbatch(B, Hkv, rep); }
-
-// v3 (one workgroup per (row, kv head), no split merge) below this many (row, kv head) pairs
-static int g_attn_v3_max_pairs = 4096;  // up to the v2 threshold: faster than the split kernels at B = 1..256 (8 kv heads)
-void attn_set_v3_max_pairs(int n) { g_attn_v3_max_pairs = n; }
-static bool use_v3(int B, int Hkv, int rep) {
-  return rep <= 8 && !use_v2(B, Hkv, rep) && B * Hkv <= g_attn_v3_max_pairs;
-}
-// v3 keys per lane-group row per chunk = base KPG (REP * KPG = 8) x this multiplier (1, 2, 4; capped at 8 rows):
-// fewer, larger chunks = fewer dependent load round trips on the latency-bound small-batch path
-// 0 = by size: x2 up to 128 (row, kv head) pairs (B <= 16 at 8 kv heads: B = 1 T = 384 12.4 -> 11.0 us, B = 8
-// 12.8 -> 11.3, B = 1 T = 1024 25.2 -> 22.1), x1 above (B = 32 / 64 slightly faster at x1;
-// profiles/r2_attn_decode_v3_kpg_ab.jsonl)
-static int g_v3_kpg_mult = 0;
-void attn_set_v3_kpg(int mult) { g_v3_kpg_mult = mult >= 4 ? 4 : (mult >= 2 ? 2 : (mult == 1 ? 1 : 0)); }
-// v5 (split small-batch kernel) below g_attn_v5_max_pairs (row, kv head) pairs, ahead of v3
-// (measured with tools/bench_attn_decode.py, profiles/r3_attn_decode_v5_vs_v3.jsonl: at rep 8 -- Llama-3-70B at MP 8 --
-// v3 is compute-bound on one CU per pair, so v5 wins 1.5-2x up to 32 pairs and further; at rep 4 -- Llama-3-8B -- the
-// two tie at 64 pairs and v3 wins at 128)
-static bool use_v5(int B, int Hkv, int rep) {
-  const int pairs = B * Hkv;
-  return rep <= 16 && (rep & (rep - 1)) == 0 &&
-         (pairs <= g_attn_v5_max_pairs || (rep >= 8 && pairs <= 4 * g_attn_v5_max_pairs));
-}
-// v6 (attn_decode_mma.hip: scores and P.V on the matrix cores, one workgroup per pair, no workspace): 0 off,
-// 1 where it wins (by shape), 2 every decode shape it supports (A/B, tests)
-// By shape (graph-timed with cold K/V, profiles/r5_attn_decode_v6_ab.jsonl): at rep 8 from 8 up to (not including)
-// 2048 (row, kv head) pairs -- Llama-3-70B at MP 8, B = 32 / 256: 12.9 / 28.8 -> 10.2 / 14.1 us; MP 1, B = 32: 39.0 ->
-// 18.7 -- the VALU kernels there are compute-bound on the 8 q heads of a pair; v4 keeps rep 8 from 2048 pairs (MP 1,
-// B = 256: 80 vs 94 us) and every rep <= 4 shape (v4 / v3 / v5 stream those faster).
-static int g_attn_v6 = 1;
-void attn_set_v6(int mode) { g_attn_v6 = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
-static bool use_v6(int B, int Hkv, int rep) {
-  if (g_attn_v6 == 0 || rep > 16 || (rep & (rep - 1))) return false;
-  if (g_attn_v6 == 2) return true;
-  return rep >= 8 && B * Hkv >= 8 && B * Hkv < 2048;
-}
-// the kernels that also write the packed output copy: v6, v5, v3, and v4 at decode rows <= 64 (mid-batch)
-int attn_decode_packs(int B, int Hkv, int rep) {
-  return (use_v6(B, Hkv, rep) || use_v5(B, Hkv, rep) || use_v3(B, Hkv, rep) || (B <= SKINNY_MAX_M && v4_midbatch(B, Hkv, rep))) ? 1 : 0;
-}
-
-int attn_decode_chunk(int B, int Hkv, int T, int rep) {
-  if (use_v6(B, Hkv, rep)) return T;
-  if (use_v5(B, Hkv, rep)) return 16 * kpg5(rep);
-  if (use_v3(B, Hkv, rep)) return T;
-  return 4 * kpg_v2(rep, B * Hkv);
-}
-
-int attn_decode_splits(int B, int Hkv, int T, int rep) {
-  if (use_v6(B, Hkv, rep)) return 1;
-  if (use_v5(B, Hkv, rep)) return (T + 16 * kpg5(rep) - 1) / (16 * kpg5(rep));
-  if (use_v3(B, Hkv, rep)) return 1;
-  if (v4_midbatch(B, Hkv, rep)) return 1;  // one split: the v4 stream (v2 with a key mask)
-  const int pairs = B * Hkv;
-  const int max_split = T > 64 ? (T + 63) / 64 : 1;  // >= 64 keys per split
-  int ns = (g_attn_waves_target + pairs - 1) / pairs;
-  ns = ns < 1 ? 1 : (ns > max_split ? max_split : ns);
-  return ns;
-}
-
+// Launches the kernel attn_decode_plan() names: each JLA_AD* row below maps plan fields to one instantiation (a plan
+// no row matches would be a bug in the plan: -1). -2: nsplit is not the plan's; -3: a packed copy this launch cannot
+// write (only v6 / v5 / v3, and v4 at decode rows <= 64, write it).
 int attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                 const uint8_t* key_mask, int mask_len, bf16_t* out, float* ws, int32_t* tickets, int B, int H,
                 int Hkv, int Dh, int T, int t_cap, int nsplit, hipStream_t s, bf16_t* out_pack) {
   if (B <= 0) return 0;
-  if (out_pack && !attn_decode_packs(B, Hkv, H / Hkv)) return -3;  // only the small-batch kernels write the packed copy
-  // (a key mask sends the mid-batch rows to v2, which does not write it)
-  if (out_pack && key_mask && !use_v6(B, Hkv, H / Hkv) && !use_v5(B, Hkv, H / Hkv) && !use_v3(B, Hkv, H / Hkv))
-    return -3;
-  if (Dh != AD_DH || H % Hkv) return -1;
-  const int rep = H / Hkv;
-  if (attn_decode_splits(B, Hkv, t_cap, rep) != nsplit) return -2;
-  if (use_v6(B, Hkv, rep))
-    return attn_decode_v6(q, kc, vc, slot, kv_start, key_mask, mask_len, out, B, H, Hkv, T, t_cap, s, out_pack);
+  const AttnPlanResult r = attn_decode_plan(g_attn_knobs, B, H, Hkv, Dh, t_cap, key_mask != nullptr);
+  if (r.rc) return r.rc;
+  const AttnPlan& p = r.plan;
+  if (p.nsplit != nsplit) return -2;
+  if (out_pack && !p.packs) return -3;
   const float scale = 1.f / sqrtf((float)Dh);
-  if (use_v5(B, Hkv, rep)) {
-    dim3 grid5(nsplit, Hkv, B);
-#define JLA_AD5(R, K)                                                                                          \
-  if (rep == R) {                                                                                              \
-    if (g_attn_v5_fold == 4 || (g_attn_v5_fold == 0 && B * Hkv < 16))                                          \
-      attn_decode_v5_kernel<R, K, 4><<<grid5, AD5_WAVES * 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask,     \
-                                                                      mask_len, out, ws, tickets, H, Hkv, T,   \
-                                                                      t_cap, nsplit, scale, out_pack);         \
-    else                                                                                                       \
-      attn_decode_v5_kernel<R, K, 12><<<grid5, AD5_WAVES * 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask,    \
-                                                                       mask_len, out, ws, tickets, H, Hkv, T,  \
-                                                                       t_cap, nsplit, scale, out_pack);        \
-    JLA_CHECK_LAUNCH();                                                                                        \
-    return 0;                                                                                                  \
-  }
-    JLA_AD5(1, 8) JLA_AD5(2, 8) JLA_AD5(4, 4) JLA_AD5(8, 2) JLA_AD5(16, 1)
-#undef JLA_AD5
-    return -1;
-  }
-  if (use_v3(B, Hkv, rep)) {
-    dim3 grid3(Hkv, B);
-#define JLA_AD3(R, K)                                                                                          \
-  if (rep == R) {                                                                                              \
-    attn_decode_v3_kernel<R, K><<<grid3, AD3_WAVES * 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, \
-                                                                 out, H, Hkv, T, t_cap, scale, out_pack);      \
-    JLA_CHECK_LAUNCH();                                                                                        \
-    return 0;                                                                                                  \
-  }
-    const int mult = g_v3_kpg_mult ? g_v3_kpg_mult : (B * Hkv <= 128 ? 2 : 1);
-    const int kpg3 = min(min(8, 16 / rep), (8 / rep) * mult);  // REP * KPG <= 16: no spills
-#define JLA_AD3K(R, K) \
-  if (kpg3 == K) {     \
-    JLA_AD3(R, K)      \
-  }
-    JLA_AD3K(1, 8) JLA_AD3K(2, 4) JLA_AD3K(2, 8) JLA_AD3K(4, 2) JLA_AD3K(4, 4) JLA_AD3K(8, 1) JLA_AD3K(8, 2)
-#undef JLA_AD3K
-#undef JLA_AD3
-    return -1;
-  }
   const int items = B * Hkv * nsplit;
-  if (g_attn_v4 && nsplit == 1 && !key_mask && rep <= 8) {
-#define JLA_AD4(R, K, U)                                                                                         \
-  if (rep == R) {                                                                                                \
-    attn_decode_v4_kernel<R, K, U><<<items, 64, 0, s>>>(q, kc, vc, slot, kv_start, out, H, Hkv, T, t_cap, scale,   \
-                                                        out_pack);                                               \
-    JLA_CHECK_LAUNCH();                                                                                          \
-    return 0;                                                                                                    \
+  switch (p.kernel) {
+    case ATTN_V6:
+      return attn_decode_v6(q, kc, vc, slot, kv_start, key_mask, mask_len, out, B, H, Hkv, T, t_cap, p.wpp, s,
+                            out_pack);
+    case ATTN_V5: {
+      const dim3 grid5(nsplit, Hkv, B);
+#define JLA_AD5(R, K, F)                                                                                            \
+  if (p.rep == R && p.kpg == K && p.fold == F) {                                                                    \
+    attn_decode_v5_kernel<R, K, F><<<grid5, AD5_WAVES * 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len,   \
+                                                                    out, ws, tickets, H, Hkv, T, t_cap, nsplit,     \
+                                                                    scale, out_pack);                               \
+    JLA_CHECK_LAUNCH();                                                                                             \
+    return 0;                                                                                                       \
   }
-    if (g_attn_diag && rep == 4) {  // tools only: stream-only build of the rep-4 kernel (wrong results)
-      attn_decode_v4_kernel<4, 4, 3, true><<<items, 64, 0, s>>>(q, kc, vc, slot, kv_start, out, H, Hkv, T, t_cap, scale,
-                                                                nullptr);
-      JLA_CHECK_LAUNCH();
-      return 0;
+      JLA_AD5(1, 8, 4) JLA_AD5(2, 8, 4) JLA_AD5(4, 4, 4) JLA_AD5(8, 2, 4) JLA_AD5(16, 1, 4)
+      JLA_AD5(1, 8, 12) JLA_AD5(2, 8, 12) JLA_AD5(4, 4, 12) JLA_AD5(8, 2, 12) JLA_AD5(16, 1, 12)
+#undef JLA_AD5
+      return -1;
     }
-    JLA_AD4(1, 4, 3) JLA_AD4(2, 4, 3) JLA_AD4(4, 4, 3)
-    // rep 8 (Llama-3-70B: 8 q heads per kv head): twice the q / o registers of rep 4, so 8-key chunks, 3 in flight
-    // (16-key chunks x 3 slots at rep 8 fail the ring check: the compiler reuses in-flight ring registers)
-    JLA_AD4(8, 2, 4)
+    case ATTN_V3: {
+      const dim3 grid3(Hkv, B);
+#define JLA_AD3(R, K)                                                                                               \
+  if (p.rep == R && p.kpg == K) {                                                                                   \
+    attn_decode_v3_kernel<R, K><<<grid3, AD3_WAVES * 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, \
+                                                                 H, Hkv, T, t_cap, scale, out_pack);                \
+    JLA_CHECK_LAUNCH();                                                                                             \
+    return 0;                                                                                                       \
+  }
+      JLA_AD3(1, 8) JLA_AD3(2, 4) JLA_AD3(2, 8) JLA_AD3(4, 2) JLA_AD3(4, 4) JLA_AD3(8, 1) JLA_AD3(8, 2)
+#undef JLA_AD3
+      return -1;
+    }
+    case ATTN_V4: {
+#define JLA_AD4(R, K, U, DIAG, PACK)                                                                                \
+  if (p.rep == R && p.kpg == K && p.ring == U) {                                                                    \
+    attn_decode_v4_kernel<R, K, U, DIAG><<<items, 64, 0, s>>>(q, kc, vc, slot, kv_start, out, H, Hkv, T, t_cap,      \
+                                                              scale, PACK);                                         \
+    JLA_CHECK_LAUNCH();                                                                                             \
+    return 0;                                                                                                       \
+  }
+      // tools only: stream-only build of the rep-4 kernel (wrong results)
+      if (g_attn_diag) JLA_AD4(4, 4, 3, true, nullptr)
+      JLA_AD4(1, 4, 3, false, out_pack) JLA_AD4(2, 4, 3, false, out_pack) JLA_AD4(4, 4, 3, false, out_pack)
+      JLA_AD4(8, 2, 4, false, out_pack)
 #undef JLA_AD4
+      return -1;
+    }
+    case ATTN_V2: {
+#define JLA_AD2M(R, K, NS, MASK)                                                                                    \
+  attn_decode_v2_kernel<R, K, NS, MASK><<<items, 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, ws, \
+                                                             tickets, B, H, Hkv, T, t_cap, nsplit, p.split_len,     \
+                                                             scale, g_attn_diag);
+#define JLA_AD2(R, K, NS)                           \
+  if (p.rep == R && p.kpg == K && p.ring == NS) {   \
+    if (key_mask) {                                 \
+      JLA_AD2M(R, K, NS, true)                      \
+    } else {                                        \
+      JLA_AD2M(R, K, NS, false)                     \
+    }                                               \
+    JLA_CHECK_LAUNCH();                             \
+    return 0;                                       \
   }
-  int split_len = (t_cap + nsplit - 1) / nsplit;
-  split_len = (split_len + 31) / 32 * 32;
-#define JLA_AD2(R, KPG, NS)                                                                                          \
-  if (key_mask)                                                                                                     \
-    attn_decode_v2_kernel<R, KPG, NS, true><<<items, 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, \
-                                                                 ws, tickets, B, H, Hkv, T, t_cap, nsplit, split_len, \
-                                                                 scale, g_attn_diag);                              \
-  else                                                                                                              \
-    attn_decode_v2_kernel<R, KPG, NS, false><<<items, 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, \
-                                                                  ws, tickets, B, H, Hkv, T, t_cap, nsplit,          \
-                                                                  split_len, scale, g_attn_diag);
-  const bool k8 = kpg_v2(rep, B * Hkv) == 8;
-  switch (rep) {
-    // REP <= 4 shares one body per geometry (REP only sizes the register arrays)
-    case 1: if (k8) { JLA_AD2(1, 8, 2) } else { JLA_AD2(1, 4, 2) } break;
-    case 2: if (k8) { JLA_AD2(2, 8, 2) } else { JLA_AD2(2, 4, 2) } break;
-    case 4: if (k8) { JLA_AD2(4, 8, 2) } else { JLA_AD2(4, 4, 2) } break;
-    case 8: JLA_AD2(8, 2, 4) break;
-    case 16: JLA_AD2(16, 1, 4) break;
-    default: return -1;
-  }
+      // REP <= 4 shares one body per geometry (REP only sizes the register arrays)
+      JLA_AD2(1, 8, 2) JLA_AD2(2, 8, 2) JLA_AD2(4, 8, 2) JLA_AD2(1, 4, 2) JLA_AD2(2, 4, 2) JLA_AD2(4, 4, 2)
+      JLA_AD2(8, 2, 4) JLA_AD2(16, 1, 4)
 #undef JLA_AD2
-  JLA_CHECK_LAUNCH();
-  return 0;
+#undef JLA_AD2M
+      return -1;
+    }
+  }
+  return -1;
 }
 
 JLA_BOUNDS_ACCESSOR(attn_decode)

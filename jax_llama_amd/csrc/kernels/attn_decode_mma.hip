@@ -163,23 +163,15 @@ __global__ void __launch_bounds__(WPP * 64)
   }
 }
 
-// waves per (row, kv head) pair: enough workgroups to cover the CUs, fewer waves (less merge) for many pairs;
-// attn_set_v6_wpp pins it (A/B)
-static int g_v6_wpp = 0;
 static int g_v6_diag = 0;
 void attn_set_v6_diag(int d) { g_v6_diag = d & 7; }
-void attn_set_v6_wpp(int wpp) { g_v6_wpp = (wpp == 1 || wpp == 2 || wpp == 4 || wpp == 8) ? wpp : 0; }
-int attn_v6_wpp(int pairs) {
-  if (g_v6_wpp) return g_v6_wpp;
-  return pairs >= 4096 ? 1 : 2;  // 2 waves were best or tied from 1 to 256 pairs (r5_attn_decode_v6_ab.jsonl)
-}
 
+// wpp: the plan's waves per (row, kv head) pair (attn_plan.h)
 int attn_decode_v6(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                    const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int H, int Hkv, int T, int t_cap,
-                   hipStream_t s, bf16_t* out_pack) {
+                   int wpp, hipStream_t s, bf16_t* out_pack) {
   const int rep = H / Hkv, pairs = B * Hkv;
   const float scale_log2 = 1.4426950408889634f / sqrtf((float)AD6_DH);
-  const int wpp = attn_v6_wpp(pairs);
   if (g_v6_diag && rep == 8 && wpp == 2) {  // tools only: the ablation instances of the 70B shape (wrong results)
 #define JLA_AD6D(D)                                                                                                \
   if (g_v6_diag == D) {                                                                                            \

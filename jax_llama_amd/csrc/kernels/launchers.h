@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "attn_plan.h"
 #include "gemm_plan.h"
 #include "gemv_plan.h"
 
@@ -129,13 +130,19 @@ int rope_kv_write(const bf16_t* qkv, const float* table, int table_len, const in
                   bf16_t* vc, const int32_t* slot, int M, int S, int H, int Hkv, int Dh, int T, bf16_t* q_out,
                   hipStream_t s);
 
-int attn_decode_chunk(int B, int Hkv, int T, int rep);
-void attn_set_v5_max_pairs(int n);
-void attn_set_v5_fold(int n);       // v5 last-arriver merge: splits per load round (12 default, 4: the first version)  // split small-batch decode kernel up to n (row, kv head) pairs (0 off, <0 default)
-void attn_set_v3_max_pairs(int n);  // single-workgroup-per-(row, kv head) decode kernel up to n pairs (0: off)
-void attn_set_impl(int impl, int waves_target);
-void attn_set_diag(int d);
-void attn_set_v3_kpg(int mult);  // small-batch decode attention: key rows per lane per chunk x mult (1, 2, 4)
+// decode attention: the process-wide knobs attn_decode() resolves its plan with (attn_plan.h AttnKnobs), the setters
+// tests and tools move them with, and the way back to the defaults
+const AttnKnobs& attn_knobs();
+void attn_reset_knobs();
+void attn_set_impl(int impl, int waves_target);  // impl 4: v2's (KPG 4, 2 slots) ring, no v4; waves_target: see there
+void attn_set_v3_max_pairs(int n);
+void attn_set_v3_kpg(int mult);
+void attn_set_v5_max_pairs(int n);  // < 0: the default
+void attn_set_v5_fold(int n);
+void attn_set_v6(int mode);
+void attn_set_v6_wpp(int wpp);
+void attn_set_diag(int d);     // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)
+void attn_set_v6_diag(int d);  // tools only: v6 ablations (1 no compute, 2 no K loads, 4 no V DMAs; wrong results)
 // bounds-checked debug build: per-translation-unit error words (JLA_BOUNDS_* bits; 0 in release builds)
 unsigned jla_bounds_norm_embed(int reset);
 unsigned jla_bounds_rope_kv(int reset);
@@ -144,20 +151,16 @@ unsigned jla_bounds_gemm(int reset);
 unsigned jla_bounds_gemv(int reset);
 unsigned jla_bounds_attn_decode(int reset);
 unsigned jla_bounds_attn_prefill(int reset);
-int attn_decode_splits(int B, int Hkv, int T, int rep);
-// ws: >= B*H*nsplit*(Dh+2) floats; tickets: B*Hkv int32, zero-initialised once (self-resetting)
+// The launch attn_decode_plan() (attn_plan.h) resolves for (knobs, shape, key mask): nsplit must be the plan's, ws and
+// tickets hold the plan's ws_floats / tickets (tickets zero-initialised once, self-resetting), out_pack only where the
+// plan packs. Returns the plan's rc where it refuses; -2 / -3 for a wrong nsplit / an out_pack the plan does not write.
 int attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                 const uint8_t* key_mask, int mask_len, bf16_t* out, float* ws, int32_t* tickets, int B, int H,
                 int Hkv, int Dh, int T, int t_cap, int nsplit, hipStream_t s, bf16_t* out_pack = nullptr);
-int attn_decode_packs(int B, int Hkv, int rep);
-// decode attention on the matrix cores (attn_decode_mma.hip); dispatched by attn_decode (attn_set_v6 mode)
+// decode attention on the matrix cores (attn_decode_mma.hip) at the plan's waves per pair; launched by attn_decode
 int attn_decode_v6(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                    const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int H, int Hkv, int T, int t_cap,
-                   hipStream_t s, bf16_t* out_pack);
-void attn_set_v6(int mode);
-void attn_set_v6_wpp(int wpp);
-void attn_set_v6_diag(int d);  // tools only: v6 ablations (1 no compute, 2 no K loads, 4 no V DMAs; wrong results)
-int attn_v6_wpp(int pairs);
+                   int wpp, hipStream_t s, bf16_t* out_pack);
 void attn_prefill_set_impl(int impl);  // 2 = GQA-shared MFMA 32x32 flash kernel (default), 1 = v1
 int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                  const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,

@@ -649,15 +649,14 @@ def linear_qkv_attention(x: torch.Tensor, w, rms_eps: Optional[float], table: to
 
 
 def attention_packs(q: torch.Tensor, k_cache: torch.Tensor, key_mask: Optional[torch.Tensor] = None) -> bool:
-    """Whether ``attention(..., out_packed=...)`` can write the packed copy for this decode shape (with a key mask
-    only the small-batch kernels, v3 / v5, do: mid-batch rows then go to v2)."""
-    bsz, s, h, _ = q.shape
+    """Whether ``attention(..., out_packed=...)`` can write the packed copy for this decode shape: the ``packs`` of
+    the launch's plan (csrc/kernels/attn_plan.h; it does not depend on how many key slots the launch covers)."""
+    bsz, s, h, dh = q.shape
     if s != 1:
         return False
-    e = ext()
-    if key_mask is not None and bsz > 32:
-        return False
-    return bool(e.attn_decode_packs(bsz, k_cache.shape[1], h // k_cache.shape[1]))
+    rc, _why, _kernel, _nsplit, packs, *_ = ext().attn_decode_plan_check(
+        bsz, h, k_cache.shape[1], dh, k_cache.shape[2], key_mask is not None)
+    return rc == 0 and bool(packs)
 
 
 def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot0, kv_start: torch.Tensor,
@@ -678,9 +677,12 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
     e = ext()
     if s == 1:
         hkv = k_cache.shape[1]
-        nsplit = e.attn_decode_splits(bsz, hkv, t_cap, h // hkv)
-        ws = workspace.get("attn_decode", bsz * h * nsplit * (dh + 4), torch.float32, q.device)
-        tickets = workspace.get_zeroed("attn_tickets", bsz * hkv, torch.int32, q.device)
+        # one plan call (csrc/kernels/attn_plan.h): the split count and what the launch needs; a shape it refuses is
+        # reported by the launch below, with the rule
+        _rc, _why, _kernel, nsplit, _packs, ws_floats, n_tickets, *_ = e.attn_decode_plan_check(
+            bsz, h, hkv, dh, t_cap, key_mask is not None)
+        ws = workspace.get("attn_decode", ws_floats, torch.float32, q.device)
+        tickets = workspace.get_zeroed("attn_tickets", n_tickets, torch.int32, q.device)
         e.attn_decode(q, k_cache, v_cache, slot_t, kv_start, key_mask, out, ws, tickets, t_cap, nsplit, out_packed)
     else:
         e.attn_prefill(q, k_cache, v_cache, slot_t, kv_start, key_mask, out)

@@ -9,7 +9,7 @@ boundary, one K term or column off, a truncated bf16 store or a wrong RoPE table
                               planted ties, quarter-turn RoPE epilogues, power-of-two fused-norm row scales.
 
 Every kernel is forced with the knobs tests/test_kernels_gpu.py uses (restored in ``finally``), and the selection is
-asserted through ``attn_decode_splits`` / ``attn_decode_packs`` / ``gemm_plan_check`` where those can tell."""
+asserted through ``attn_decode_plan_check`` / ``gemm_plan_check``."""
 from __future__ import annotations
 
 import contextlib
@@ -34,42 +34,39 @@ STORE, RESID, SWIGLU, QKV = ops.MODE_STORE, ops.MODE_RESIDUAL, ops.MODE_SWIGLU, 
 # ======================================================================================
 # A / B. attention
 # ======================================================================================
-def _restore_decode_knobs(e):
-    """The values attn_decode.hip starts with."""
-    e.attn_set_impl(2, 0)
-    e.attn_set_v5_max_pairs(-1)
-    e.attn_set_v5_fold(0)
-    e.attn_set_v3_kpg(0)
-    e.attn_set_v3_max_pairs(4096)
-    e.attn_set_v6(1)
-    e.attn_set_v6_wpp(0)
-
-
 KPG5 = {1: 8, 2: 8, 4: 4, 8: 2, 16: 1}  # v5 keys per lane group: a split holds 16 x this many keys
+
+
+def _plan(e, b, hkv, t, rep, masked):
+    """(kernel name, splits, packs) of the decode launch under the current knobs (csrc/kernels/attn_plan.h)."""
+    rc, why, kernel, nsplit, packs, *_ = e.attn_decode_plan_check(b, hkv * rep, hkv, DH, t, masked)
+    assert rc == 0, why
+    return kernel, nsplit, packs
 
 
 @contextlib.contextmanager
 def _decode_kernel(kernel, knob, b, hkv, t, rep, masked):
-    """Force one decode kernel and assert, as far as the query functions can tell, that the dispatcher selects it.
-    Yields whether the kernel writes the packed output copy.
+    """Force one decode kernel and assert that the dispatcher's plan selects it. Yields whether the kernel writes the
+    packed output copy.
 
     v2: ``attn_set_impl(2, -1)`` / ``(4, 0)`` alone do not reach v2 at 6 (row, kv head) pairs -- the dispatcher asks
     v5, then v3 first -- so those two are switched off as well; then nothing packs and the keys are cut into >= 2
-    splits from T = 65 on (with one split, no mask and impl 2 the dispatcher runs the v4 ring instead: T = 40)."""
+    splits from T = 65 on (with one split, no mask, rep <= 8 and impl 2 the dispatcher runs the v4 ring instead:
+    T = 40)."""
     e = ops.ext()
     try:
         if kernel == "v3":
             e.attn_set_v5_max_pairs(0)
             e.attn_set_v3_kpg(knob)
-            assert e.attn_decode_splits(b, hkv, t, rep) == 1 and e.attn_decode_packs(b, hkv, rep)
+            assert _plan(e, b, hkv, t, rep, masked) == ("v3", 1, True)
         elif kernel == "v5":
             e.attn_set_v5_max_pairs(4096)
             e.attn_set_v5_fold(knob)
-            assert e.attn_decode_splits(b, hkv, t, rep) == -(-t // (16 * KPG5[rep])) and e.attn_decode_packs(b, hkv, rep)
+            assert _plan(e, b, hkv, t, rep, masked) == ("v5", -(-t // (16 * KPG5[rep])), True)
         elif kernel == "v6":
             e.attn_set_v6(2)
             e.attn_set_v6_wpp(knob)
-            assert e.attn_decode_splits(b, hkv, t, rep) == 1 and e.attn_decode_packs(b, hkv, rep)
+            assert _plan(e, b, hkv, t, rep, masked) == ("v6", 1, True)
         elif kernel == "v2":
             e.attn_set_v5_max_pairs(0)
             e.attn_set_v3_max_pairs(0)
@@ -77,16 +74,18 @@ def _decode_kernel(kernel, knob, b, hkv, t, rep, masked):
                 e.attn_set_impl(2, -1)
             else:
                 e.attn_set_impl(4, 0)
-            assert not e.attn_decode_packs(b, hkv, rep)
-            assert (e.attn_decode_splits(b, hkv, t, rep) > 1) == (t > 64)
+            name, nsplit, packs = _plan(e, b, hkv, t, rep, masked)
+            assert name == ("v4" if knob == 2 and t <= 64 and not masked and rep <= 8 else "v2")
+            assert not packs
+            assert (nsplit > 1) == (t > 64)
         elif kernel == "v4":
-            assert e.attn_decode_splits(b, hkv, t, rep) == 1 and not masked
-            assert bool(e.attn_decode_packs(b, hkv, rep)) == (b <= 64)
+            assert not masked
+            assert _plan(e, b, hkv, t, rep, masked) == ("v4", 1, b <= 64)
         else:
             raise AssertionError(kernel)
-        yield bool(e.attn_decode_packs(b, hkv, rep))
+        yield _plan(e, b, hkv, t, rep, masked)[2]
     finally:
-        _restore_decode_knobs(e)
+        e.attn_reset_knobs()
 
 
 def _attend(q, kd, vd, slot0, kvs_d, mask_d, packs):

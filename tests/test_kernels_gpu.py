@@ -168,14 +168,14 @@ def test_attention_decode_streaming_v2(rep, t, slot, masked):
         e.attn_set_impl(2, -1)  # v2 for any batch size ...
         e.attn_set_v5_max_pairs(0)  # ... once the small-batch kernels the dispatcher asks first (v5, then v3) are off
         e.attn_set_v3_max_pairs(0)
-        assert not e.attn_decode_packs(b, hkv, rep)  # (v6 / v5 / v3 would write the packed copy)
+        # the plan: v2, which never writes the packed copy -- but with one split (T <= 64) and no mask the v4 ring
+        _, _, kernel, nsplit, packs, *_ = e.attn_decode_plan_check(b, h, hkv, dh, t, masked)
+        assert kernel == ("v4" if t <= 64 and not masked else "v2") and (nsplit > 1) == (t > 64) and not packs
         got = ops.attention(q.to(DEV), kc.to(DEV), vc.to(DEV), torch.tensor([slot], dtype=torch.int32, device=DEV),
                             kv_start.to(DEV), None if mask is None else mask.to(DEV))
         torch.cuda.synchronize()
     finally:
-        e.attn_set_impl(2, 0)
-        e.attn_set_v5_max_pairs(-1)
-        e.attn_set_v3_max_pairs(4096)
+        e.attn_reset_knobs()
     _close(got, expect, 2e-2, 2e-2)
     assert got[2].float().abs().max().item() == 0.0
 
@@ -186,7 +186,7 @@ def test_attention_decode_streaming_v2(rep, t, slot, masked):
 def test_attention_decode_v4_large_batch(rep, t, slot, b):
     """Large batch, one split, no key mask: the register-ring streaming kernel (v4) serves it (from 4096 (row, kv
     head) pairs, and mid-batch above 64 rows: every rep <= 4, rep 8 from 2048 pairs); compare with the fp32 reference
-    and with the v2 LDS-DMA kernel (impl 4)."""
+    and with what impl 4 runs instead (the v2 LDS-DMA kernel from 4096 pairs, v3 below)."""
     e = ops.ext()
     hkv, dh = 8, 128
     h = hkv * rep
@@ -197,14 +197,19 @@ def test_attention_decode_v4_large_batch(rep, t, slot, b):
     kv_start[7] = slot + 1  # a row with no valid key -> zeros
     expect = ref.attention(q, kc, vc, slot, kv_start).reshape(b, h * dh)
     args = (q.to(DEV), kc.to(DEV), vc.to(DEV), torch.tensor([slot], dtype=torch.int32, device=DEV), kv_start.to(DEV))
-    assert e.attn_decode_splits(b, hkv, t, rep) == 1
+    # the plan: v4, but v6 keeps rep 8 below 2048 pairs (B = 128). Under impl 4 (no v4): v2 from 4096 pairs (B = 512),
+    # below that what the dispatcher asks first -- v6 as before, else v3
+    pairs, v6 = b * hkv, rep == 8 and b * hkv < 2048
+    assert e.attn_decode_plan_check(b, h, hkv, dh, t, False)[2:4] == ("v6" if v6 else "v4", 1)
     got = ops.attention(*args)
     try:
         e.attn_set_impl(4, 0)  # v2, (4-key group, 2 slots)
+        assert e.attn_decode_plan_check(b, h, hkv, dh, t, False)[2:4] == (
+            "v2" if pairs >= 4096 else ("v6" if v6 else "v3"), 1)
         got_v2 = ops.attention(*args)
         torch.cuda.synchronize()
     finally:
-        e.attn_set_impl(2, 0)
+        e.attn_reset_knobs()
     _close(got, expect, 2e-2, 2e-2)
     assert got[7].float().abs().max().item() == 0.0
     _close(got, got_v2, 1e-2, 1e-2)
@@ -845,6 +850,7 @@ def test_attention_decode_small_batch_kernels(kernel, rep, t, slot, masked):
         qd = q.to(DEV)
         kd, vd = kc.to(DEV), vc.to(DEV)
         assert ops.attention_packs(qd, kd)
+        assert e.attn_decode_plan_check(b, h, hkv, dh, t, masked)[2] == kernel
         packed = ops.packed_empty(b, h * dh, DEV)
         got = ops.attention(qd, kd, vd, torch.tensor([slot], dtype=torch.int32, device=DEV), kv_start.to(DEV),
                             None if mask is None else mask.to(DEV), out_packed=packed)
@@ -852,7 +858,7 @@ def test_attention_decode_small_batch_kernels(kernel, rep, t, slot, masked):
                               None if mask is None else mask.to(DEV))
         torch.cuda.synchronize()
     finally:
-        e.attn_set_v5_max_pairs(-1)
+        e.attn_reset_knobs()
     _close(got, expect, 2e-2, 2e-2)
     assert torch.equal(got, again)  # tickets reset themselves: a second call merges the same way
     if not masked:
@@ -887,14 +893,13 @@ def test_attention_decode_mfma_v6(wpp, rep, t, slot, masked):
         qd, kd, vd = q.to(DEV), kc.to(DEV), vc.to(DEV)
         sl = torch.tensor([slot], dtype=torch.int32, device=DEV)
         md = None if mask is None else mask.to(DEV)
-        assert e.attn_decode_splits(b, hkv, t, rep) == 1 and e.attn_decode_packs(b, hkv, rep)
+        assert e.attn_decode_plan_check(b, h, hkv, dh, t, masked)[2:5] == ("v6", 1, True)
         packed = ops.packed_empty(b, h * dh, DEV)
         got = ops.attention(qd, kd, vd, sl, kv_start.to(DEV), md, out_packed=packed)
         again = ops.attention(qd, kd, vd, sl, kv_start.to(DEV), md)
         torch.cuda.synchronize()
     finally:
-        e.attn_set_v6(0)
-        e.attn_set_v6_wpp(0)
+        e.attn_reset_knobs()
     _close(got, expect, 2e-2, 2e-2)
     assert torch.equal(got, again)
     if not masked:

@@ -26,25 +26,21 @@ from jax_llama_amd.config import get_preset  # noqa: E402
 
 
 def set_impl(e, impl):
-    e.attn_set_impl(2, 4096)
+    e.attn_reset_knobs()
     # 60: the MFMA kernel (v6) with its default waves per pair; 61 / 62 / 64 / 68: v6 with 1 / 2 / 4 / 8 waves per pair
     # 600 + d: v6 at 2 waves per pair with ablation d (attn_set_v6_diag: 1 no compute, 2 no K loads, 4 no V DMAs)
-    if hasattr(e, "attn_set_v6_diag"):
-        e.attn_set_v6_diag(impl - 600 if 601 <= impl <= 607 else 0)
+    e.attn_set_v6_diag(impl - 600 if 601 <= impl <= 607 else 0)
     if 601 <= impl <= 607:
         impl = 62
     e.attn_set_v6(2 if 60 <= impl <= 68 else 0)
     e.attn_set_v6_wpp(impl - 60 if 61 <= impl <= 68 else 0)
-    e.attn_set_v3_max_pairs(4096)
     if impl in (7, 9):
         # the streaming kernels at any pair count, one split: 7 = v4 register ring, 9 = v2 (LDS-DMA ring)
         e.attn_set_impl(4 if impl == 9 else 2, 1)  # waves target 1 -> one split
         e.attn_set_impl(4 if impl == 9 else 2, -1)  # v2/v4 down to 1 pair
         e.attn_set_v3_max_pairs(0)
-    if hasattr(e, "attn_set_v5_max_pairs"):
-        e.attn_set_v5_max_pairs(4096 if impl in (5, 6) else (0 if impl in (3, 7, 9) else -1))
-    if hasattr(e, "attn_set_v5_fold"):
-        e.attn_set_v5_fold(4 if impl == 6 else (12 if impl == 5 else 0))
+    e.attn_set_v5_max_pairs(4096 if impl in (5, 6) else (0 if impl in (3, 7, 9) else -1))
+    e.attn_set_v5_fold(4 if impl == 6 else (12 if impl == 5 else 0))
 
 
 def main():
@@ -87,7 +83,8 @@ def main():
                 for _ in range(args.reps):
                     flush.fill_(1)
             graphs[impl] = (ga, gf, diff)
-        set_impl(e, 2)
+        e.attn_set_v6_diag(0)
+        e.attn_reset_knobs()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         best = {impl: float("inf") for impl in args.impls}
         for _ in range(args.rounds):

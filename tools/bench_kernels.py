@@ -124,20 +124,18 @@ def main():
         for (impl, target), kpg in [(it, kk) for it in args.attn_impls for kk in args.v3_kpg]:
             e.attn_set_diag(1 if impl >= 100 else 0)  # 100 + impl: diagnostic stream-only run of impl
             impl = impl % 100
+            e.attn_reset_knobs()
             e.attn_set_impl(impl, target)
             e.attn_set_v3_kpg(kpg)
-            e.attn_set_v3_max_pairs(4096)
             us = timeit(lambda i: ops.attention(q, kc, vc, slot, ks))
             o = ops.attention(q, kc, vc, slot, ks).float()
             ref_out = o if ref_out is None else ref_out
             print(json.dumps({"op": "attn_decode", "impl": impl, "waves_target": target, "v3_kpg": kpg, "b": b, "t": t,
-                              "nsplit": e.attn_decode_splits(b, hkv, t, h // hkv), "us": round(us, 2),
+                              "nsplit": e.attn_decode_plan_check(b, h, hkv, hd, t, False)[3], "us": round(us, 2),
                               "TBps": round(nbytes / us / 1e6, 3),
                               "max_diff_vs_first": round(float((o - ref_out).abs().max()), 5)}), flush=True)
         e.attn_set_diag(0)
-        e.attn_set_impl(2, 4096)
-        e.attn_set_v3_kpg(0)
-        e.attn_set_v3_max_pairs(4096)
+        e.attn_reset_knobs()
         del kc, vc
 
 

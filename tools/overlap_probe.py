@@ -47,15 +47,12 @@ def main():
     ap.add_argument("--keys", type=int, default=256)
     ap.add_argument("--op", default="gate_up", choices=["gate_up", "down", "o", "qkv"])
     ap.add_argument("--tiles", type=int, nargs="+", default=[16, 17, 14, 7])
-    ap.add_argument("--attn-v", type=int, default=0, help="attn_set_v7 mode (0 = default dispatch)")
     ap.add_argument("--diag", action="store_true", help="attention: the stream-only build (no math; wrong results)")
     args = ap.parse_args()
     cfg = get_preset(args.model)
     d, f, hd = cfg.hidden_size, cfg.intermediate_size, cfg.head_dim
     h, hkv = cfg.num_attention_heads, cfg.num_key_value_heads
     e = ops.ext()
-    if args.attn_v and hasattr(e, "attn_set_v7"):
-        e.attn_set_v7(args.attn_v)
     if args.diag:
         e.attn_set_diag(1)
     m = args.m
