@@ -35,9 +35,10 @@ PROMPTS = ["The capital of Germany is the city of",
 
 
 def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int = 2048, weights: str = "bf16",
-         **model_kwargs) -> LLaMA:
+         kv_cache: str = "bf16", **model_kwargs) -> LLaMA:
     """Reference ``load`` (jax_example.py:10-31) on the MI355X runtime. ``weights="fp8"``: the layer projections are
-    quantised to FP8 e4m3 after loading (``LLaMAForCausalLM.quantize_weights_``; each rank its own shard)."""
+    quantised to FP8 e4m3 after loading (``LLaMAForCausalLM.quantize_weights_``; each rank its own shard).
+    ``kv_cache="fp8"``: the KV caches hold FP8 e4m3 rows (``LLaMAForCausalLM.set_kv_cache_format``)."""
     ctx = init_distributed()
     ctx.setup_mesh(tp=ctx.world)
     with open(os.path.join(ckpt_dir, "params.json")) as f:
@@ -50,13 +51,15 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
     del params
     if weights == "fp8":
         model.quantize_weights_("fp8_e4m3")
+    if kv_cache == "fp8":
+        model.set_kv_cache_format("fp8_e4m3")
     return LLaMA(None, model, tokenizer, mesh=Mesh(dp=1, mp=ctx.tp_size, rank=ctx.rank))
 
 
 def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int = 256, temperature: float = 0.8,
-         top_p: float = 0.95, weights: str = "bf16"):
+         top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16"):
     """Reference ``main`` (jax_example.py:33-40)."""
-    generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights)
+    generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache)
     results = generator.generate_from_str(PROMPTS, max_gen_len=max_gen_len, temperature=temperature, top_p=top_p)
     if int(os.environ.get("RANK", "0")) == 0:
         for result in results:
@@ -66,7 +69,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 
 
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
-              weights: str = "bf16"):
+              weights: str = "bf16", kv_cache: str = "bf16"):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -76,6 +79,8 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
     model = LLaMAForCausalLM(cfg, device=ctx.device, comm=comm, _do_init=False).init_random(seed=0)
     if weights == "fp8":
         model.quantize_weights_("fp8_e4m3")
+    if kv_cache == "fp8":
+        model.set_kv_cache_format("fp8_e4m3")
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
                          dtype=torch.int32)
     gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0,
@@ -85,7 +90,7 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
     torch.cuda.synchronize() if torch.cuda.is_available() else None
     dt = time.perf_counter() - t0
     if ctx.rank == 0:
-        print(f"{model_name} ({weights} weights, {model.weight_bytes() / 2**30:.2f} GiB): {batch} x {max_gen_len} tokens in {dt:.3f} s "
+        print(f"{model_name} ({weights} weights, {model.weight_bytes() / 2**30:.2f} GiB; {kv_cache} KV cache): {batch} x {max_gen_len} tokens in {dt:.3f} s "
               f"({batch * max_gen_len / dt:.1f} tok/s incl. prefill + graph capture)")
         print("first row:", seq[0, prompt_len:prompt_len + 16].tolist())
 
@@ -104,10 +109,13 @@ if __name__ == "__main__":
     ap.add_argument("--prompt_len", type=int, default=16)
     ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: FP8 e4m3 weight-only layer projections (one power-of-two scale per output row)")
+    ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
+                    help="fp8: KV caches of FP8 e4m3 rows (one power-of-two scale per row, kv head and slot): 132 bytes "
+                    "per 128-value row instead of 256")
     a = ap.parse_args()
     if a.synthetic:
-        synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights)
+        synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
-        main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights)
+        main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache)

@@ -574,6 +574,88 @@ void attn_prefill(Tensor q, Tensor kc, Tensor vc, Tensor slot, Tensor kv_start, 
      "attn_prefill");
 }
 
+// ---- the FP8 (e4m3) KV cache (kernels/kv8.hip): q bytes uint8 [B, Hkv, T, 128], scales fp32 [B, Hkv, T]
+static void check_kv8(const Tensor& kq, const Tensor& ks, const Tensor& vq, const Tensor& vs, int64_t b, int64_t hkv,
+                      const char* who) {
+  for (auto* t : {&kq, &ks, &vq, &vs}) check_gpu(*t, who);
+  check(kq.scalar_type() == torch::kUInt8 && vq.scalar_type() == torch::kUInt8 && kq.dim() == 4 && kq.size(0) == b &&
+            kq.size(1) == hkv && kq.size(2) > 0 && kq.size(3) == jla::ATTN_DH && vq.sizes() == kq.sizes(),
+        "fp8 KV cache: q bytes must be uint8 [B, Hkv, T, 128]");
+  for (auto* t : {&ks, &vs})
+    check(t->scalar_type() == torch::kFloat32 && t->dim() == 3 && t->size(0) == b && t->size(1) == hkv &&
+              t->size(2) == kq.size(2),
+          "fp8 KV cache: scales must be fp32 [B, Hkv, T]");
+}
+
+void rope_kv_write_q8(Tensor qkv, Tensor table, Tensor positions, Tensor kq, Tensor ks, Tensor vq, Tensor vs,
+                      Tensor slot, int64_t seq_len, int64_t h, int64_t hkv, int64_t dh, Tensor q) {
+  for (auto* t : {&qkv, &table, &positions, &slot, &q}) check_gpu(*t, "rope_kv_write_q8 arg");
+  check(qkv.scalar_type() == torch::kBFloat16 && q.scalar_type() == torch::kBFloat16, "rope_kv_write_q8 bf16 tensors");
+  check(dh == jla::ATTN_DH, "rope_kv_write_q8: Dh == 128");
+  check(table.scalar_type() == torch::kFloat32 && table.dim() == 3 && table.size(0) > 0 && table.size(1) == dh / 2 &&
+            table.size(2) == 2,
+        "rope table must be fp32 [L, Dh/2, 2]");
+  check(positions.scalar_type() == torch::kInt32 && slot.scalar_type() == torch::kInt32 && slot.numel() >= 1,
+        "int32 positions/slot");
+  const int64_t m = qkv.size(0);
+  check(h > 0 && hkv > 0 && qkv.dim() == 2 && qkv.size(1) == (h + 2 * hkv) * dh, "qkv shape");
+  check(seq_len > 0 && positions.numel() == m && m % seq_len == 0, "positions shape");
+  check_kv8(kq, ks, vq, vs, m / seq_len, hkv, "rope_kv_write_q8 cache");
+  check(q.numel() == m * h * dh, "q out shape");
+  rc(jla::rope_kv_write_q8(cbf(qkv), ptr<float>(table), table.size(0), ptr<int32_t>(positions), ptr<uint8_t>(kq),
+                           ptr<float>(ks), ptr<uint8_t>(vq), ptr<float>(vs), ptr<int32_t>(slot), m, seq_len, h, hkv, dh,
+                           kq.size(2), bf(q), stream()),
+     "rope_kv_write_q8");
+}
+
+// slots [0, n) of K and V as bf16 kout / vout [B, Hkv, n_out, 128], n <= n_out (rows past n are left as they are)
+void kv8_dequant(Tensor kq, Tensor ks, Tensor vq, Tensor vs, int64_t n, Tensor kout, Tensor vout) {
+  check(kq.dim() == 4, "kv8_dequant: q bytes must be uint8 [B, Hkv, T, 128]");
+  const int64_t b = kq.size(0), hkv = kq.size(1);
+  check_kv8(kq, ks, vq, vs, b, hkv, "kv8_dequant cache");
+  check_gpu(kout, "kout");
+  check_gpu(vout, "vout");
+  check(kout.scalar_type() == torch::kBFloat16 && vout.scalar_type() == torch::kBFloat16 && kout.dim() == 4 &&
+            kout.size(0) == b && kout.size(1) == hkv && kout.size(3) == jla::ATTN_DH && vout.sizes() == kout.sizes(),
+        "kv8_dequant: outputs must be bf16 [B, Hkv, n_out, 128]");
+  check(n >= 0 && n <= kq.size(2) && n <= kout.size(2), "kv8_dequant: n within the cache and the outputs");
+  check(b * hkv <= INT32_MAX && kq.size(2) <= INT32_MAX, "kv8_dequant: sizes");
+  rc(jla::kv8_dequant(ptr<uint8_t>(kq), ptr<float>(ks), ptr<uint8_t>(vq), ptr<float>(vs), bf(kout), bf(vout), b * hkv,
+                      kq.size(2), n, kout.size(2), stream()),
+     "kv8_dequant");
+}
+
+void attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor slot, Tensor kv_start,
+                    c10::optional<Tensor> key_mask, Tensor out, int64_t t_cap) {
+  for (auto* t : {&q, &slot, &kv_start, &out}) check_gpu(*t, "attn_decode_q8 arg");
+  check(q.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16 && q.dim() == 4 && q.size(1) == 1,
+        "attn_decode_q8: q bf16 [B, 1, H, Dh]");
+  const int64_t b = q.size(0), h = q.size(2), dh = q.size(3);
+  check(kq.dim() == 4, "attn_decode_q8: q bytes must be uint8 [B, Hkv, T, 128]");
+  const int64_t hkv = kq.size(1), T = kq.size(2);
+  check_kv8(kq, ks, vq, vs, b, hkv, "attn_decode_q8 cache");
+  check(slot.scalar_type() == torch::kInt32 && slot.numel() >= 1 && kv_start.scalar_type() == torch::kInt32 &&
+            kv_start.numel() == b,
+        "slot/kv_start");
+  check(out.numel() == q.numel(), "attention out shape");
+  check(t_cap >= 0 && t_cap <= T, "t_cap exceeds the cache length");
+  check(b <= 65535, "attn_decode_q8: at most 65535 rows");
+  if (key_mask.has_value()) {
+    check_gpu(*key_mask, "key_mask");
+    check(key_mask->scalar_type() == torch::kUInt8 && key_mask->dim() == 2 && key_mask->size(0) == b,
+          "key_mask must be uint8 [B, L]");
+  }
+  const jla::AttnQ8PlanResult r =
+      jla::attn_decode_q8_plan(jla::attn_knobs(), b, h, hkv, dh, t_cap, key_mask.has_value());
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: attn_decode_q8: no plan (", r.why, "; see attn_plan.h)");
+  const uint8_t* km = key_mask.has_value() ? ptr<uint8_t>(*key_mask) : nullptr;
+  const int ml = key_mask.has_value() ? key_mask->size(1) : 0;
+  rc(jla::attn_decode_q8(cbf(q), ptr<uint8_t>(kq), ptr<float>(ks), ptr<uint8_t>(vq), ptr<float>(vs),
+                         ptr<int32_t>(slot), ptr<int32_t>(kv_start), km, ml, bf(out), b, h, hkv, dh, T, t_cap,
+                         stream()),
+     "attn_decode_q8");
+}
+
 void argmax(Tensor logits, Tensor idx, Tensor val) {
   check_gpu(logits, "logits");
   check_gpu(idx, "idx");
@@ -1007,7 +1089,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("bounds_error", [](bool reset) {
     const int r = reset ? 1 : 0;
     return (int64_t)(jla::jla_bounds_norm_embed(r) | jla::jla_bounds_rope_kv(r) | jla::jla_bounds_sample(r) |
-                     jla::jla_bounds_gemm(r) | jla::jla_bounds_gemv(r) |
+                     jla::jla_bounds_gemm(r) | jla::jla_bounds_gemv(r) | jla::jla_bounds_kv8(r) |
                      jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_prefill(r));
   }, "OR of the bounds-checked debug build's error words (JLA_BOUNDS_* bits); always 0 in a release build",
         py::arg("reset") = false);
@@ -1061,6 +1143,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("attn_prefill", &attn_prefill, py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("slot"),
         py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"));
   m.def("attn_prefill_set_impl", [](int64_t impl) { jla::attn_prefill_set_impl((int)impl); });
+  // the FP8 (e4m3) KV cache (kernels/kv8.hip)
+  m.def("rope_kv_write_q8", &rope_kv_write_q8, py::arg("qkv"), py::arg("table"), py::arg("positions"), py::arg("kq"),
+        py::arg("ks"), py::arg("vq"), py::arg("vs"), py::arg("slot"), py::arg("seq_len"), py::arg("h"), py::arg("hkv"),
+        py::arg("dh"), py::arg("q"));
+  m.def("kv8_dequant", &kv8_dequant, py::arg("kq"), py::arg("ks"), py::arg("vq"), py::arg("vs"), py::arg("n"),
+        py::arg("kout"), py::arg("vout"));
+  m.def("attn_decode_q8", &attn_decode_q8, py::arg("q"), py::arg("kq"), py::arg("ks"), py::arg("vq"), py::arg("vs"),
+        py::arg("slot"), py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"), py::arg("t_cap"));
+  // (rc, why, waves, kpg, rep) of the fp8-cache decode-attention launch under the current knobs (kernels/attn_plan.h)
+  m.def("attn_decode_q8_plan_check", [](int64_t b, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap, bool masked) {
+    const jla::AttnQ8PlanResult r =
+        jla::attn_decode_q8_plan(jla::attn_knobs(), (int)b, (int)h, (int)hkv, (int)dh, (int)t_cap, masked);
+    return py::make_tuple(r.rc, r.why, r.plan.waves, r.plan.kpg, r.plan.rep);
+  }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"));
+  m.def("attn_set_q8_waves", [](int64_t w) { jla::attn_set_q8_waves((int)w); },
+        "waves per pair of the fp8-cache decode attention pinned to 1 / 8 (tests, A/B); 0: by shape");
   m.def("argmax", &argmax);
   m.def("topk_chunks", [](int64_t v) { return jla::topk_chunks(v); });
   m.def("car_alloc", &car_alloc);

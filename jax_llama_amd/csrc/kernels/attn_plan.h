@@ -28,6 +28,7 @@ struct AttnKnobs {
   int waves_target = 2048;  // v2 splits the keys until pairs x splits reaches this many waves
   bool v4 = true;           // the register-ring stream (v4); impl 4 turns it off (v2 everywhere v4 would run)
   bool v2_kpg4 = false;     // impl 4: v2's (KPG 4, 2 slots) ring at rep <= 4 for every size, not only from 16384 pairs
+  int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8; 0 = by shape
 };
 
 enum AttnKernel { ATTN_V2 = 2, ATTN_V3, ATTN_V4, ATTN_V5, ATTN_V6 };
@@ -155,6 +156,43 @@ inline AttnPlanResult attn_decode_plan(const AttnKnobs& k, int B, int H, int Hkv
   // (profiles/attn_plan_resolver_headline.jsonl).
   p.ws_floats = (size_t)B * H * p.nsplit * (ATTN_DH + 4);
   p.tickets = pairs;
+  return {0, "", p};
+}
+
+// ---- the FP8 (e4m3) KV cache (kv8.hip): one kernel template, attn_decode_q8_kernel, one workgroup per (row, kv head)
+// pair straight on the fp8 bytes; no key splits, no workspace, no tickets, no packed copy. Every rule of that launch:
+constexpr int ATTN_Q8_ONE_WAVE_MIN_PAIRS = 2048;  // one wave per pair from here (B = 256 at 8 kv heads); see the rule
+struct AttnQ8Plan {
+  int rep;    // query heads per kv head
+  int waves;  // waves per pair: 8 (v3's structure) or 1 (large batches, as v4 serves them for bf16)
+  int kpg;    // key rows per lane group per chunk
+};
+struct AttnQ8PlanResult {
+  int rc;           // 0 legal; -1 not
+  const char* why;  // the rule that refused the call
+  AttnQ8Plan plan;
+};
+inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, int Hkv, int Dh, int t_cap, bool masked) {
+  const auto fail = [](const char* why) { return AttnQ8PlanResult{-1, why, AttnQ8Plan{}}; };
+  (void)t_cap, (void)masked;  // no rule depends on them yet (no key splits; both wave forms take a key mask)
+  if (Dh != ATTN_DH) return fail("head dim: Dh == 128");
+  if (H < 1 || Hkv < 1 || H % Hkv) return fail("GQA: H a positive multiple of Hkv");
+  const int rep = H / Hkv, pairs = B * Hkv;
+  if (rep > 8 || (rep & (rep - 1))) return fail("fp8 KV cache: query heads per kv head 1, 2, 4 or 8");
+  AttnQ8Plan p{};
+  p.rep = rep;
+  // One wave per pair from 2048 pairs, 8 waves below. The rule started as the bf16 plan's v3 / v4 boundary (1 wave where
+  // rep <= 4 && B > 32, or from 4096 pairs) and moved on these records (profiles/kv8_attn_decode_ab.jsonl; graph-timed,
+  // cold K / V, medians of 7 rounds, us at 8 waves / 1 wave), T = 384 unless noted:
+  //   rep 4 (Llama-3-8B, 8 kv heads)  B = 64: 27.1 / 34.4   B = 128: 49.4 / 51.1   B = 256: 87.7 / 82.3
+  //                                   B = 512: 160 / 151    B = 2048: 581 / 414    B = 4096: 1142 / 805
+  //                                   B = 64 at T = 8192: 318 / 659
+  //   rep 8 (Llama-3-70B, 8 kv heads) B = 32: 19.7 / 65.6   B = 256: 143.5 / 102.6
+  // so 512 and 1024 pairs (where the old rule ran 1 wave at rep 4) stay with 8 waves, and rep 8 at 2048 pairs (where it
+  // ran 8) takes 1. Few pairs with a long context want the 8 waves all the more; a lone pair still runs on one CU.
+  p.waves = k.q8_waves ? k.q8_waves : (pairs >= ATTN_Q8_ONE_WAVE_MIN_PAIRS ? 1 : 8);
+  // 16 scores per query-head set and lane group at most (rep x KPG <= 16, the v3 bound: no spills), 8 rows at most
+  p.kpg = rep <= 2 ? 8 : 16 / rep;
   return {0, "", p};
 }
 

@@ -172,6 +172,19 @@ JLA_DEV float row16_sum(float v) {
   v += dppf<0x140>(v);  // row_mirror           (other half of the row)
   return v;
 }
+// Its max sibling on unsigned words (the fp32 bits of non-negative values order like the values): the row's largest,
+// in every lane.
+template <int CTRL>
+JLA_DEV uint32_t dppu(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, false);
+}
+JLA_DEV uint32_t row16_max_u32(uint32_t v) {
+  v = max(v, dppu<0xB1>(v));
+  v = max(v, dppu<0x4E>(v));
+  v = max(v, dppu<0x141>(v));
+  v = max(v, dppu<0x140>(v));
+  return v;
+}
 
 // Host-side error check used by every launcher.
 #define JLA_CHECK_LAUNCH()                                                        \

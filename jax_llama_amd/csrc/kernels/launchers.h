@@ -141,6 +141,7 @@ void attn_set_v5_max_pairs(int n);  // < 0: the default
 void attn_set_v5_fold(int n);
 void attn_set_v6(int mode);
 void attn_set_v6_wpp(int wpp);
+void attn_set_q8_waves(int waves);  // the fp8 KV cache's kernel: 1 / 8 waves per pair pinned; 0: by shape
 void attn_set_diag(int d);     // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)
 void attn_set_v6_diag(int d);  // tools only: v6 ablations (1 no compute, 2 no K loads, 4 no V DMAs; wrong results)
 // bounds-checked debug build: per-translation-unit error words (JLA_BOUNDS_* bits; 0 in release builds)
@@ -161,6 +162,22 @@ int attn_decode(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32
 int attn_decode_v6(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                    const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int H, int Hkv, int T, int t_cap,
                    int wpp, hipStream_t s, bf16_t* out_pack);
+// ---- the FP8 (e4m3) KV cache (kv8.hip): per layer q bytes uint8 [B, Hkv, T, 128] (natural element order) and one
+// power-of-two fp32 scale per (row, kv head, slot) [B, Hkv, T], for K (post-RoPE) and for V
+unsigned jla_bounds_kv8(int reset);
+// rope_kv_write with the quantising store: q rotated to q_out as there; each k / v head row quantised by the rule of
+// ops/reference.py quantize_fp8_rows from its bf16 value. Dh == 128.
+int rope_kv_write_q8(const bf16_t* qkv, const float* table, int table_len, const int32_t* positions, uint8_t* kq,
+                     float* ks, uint8_t* vq, float* vs, const int32_t* slot, int M, int S, int H, int Hkv, int Dh,
+                     int T, bf16_t* q_out, hipStream_t s);
+// slots [0, n) of every (row, kv head) pair -> bf16 kout / vout [pairs, n_out, 128] (n <= n_out; rows past n untouched)
+int kv8_dequant(const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs, bf16_t* kout, bf16_t* vout,
+                int pairs, int T, int n, int n_out, hipStream_t s);
+// decode attention on the fp8 bytes, launched as attn_decode_q8_plan() (attn_plan.h) says; returns the plan's rc where
+// it refuses
+int attn_decode_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs,
+                   const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
+                   int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s);
 void attn_prefill_set_impl(int impl);  // 2 = GQA-shared MFMA 32x32 flash kernel (default), 1 = v1
 int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                  const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,

@@ -32,7 +32,7 @@ from ..config import LLaMAConfig
 from ..ops import reference as ref
 from ..parallel.comm import NO_COMM, TPComm
 from ..parallel.partition import shard_tree
-from .kv_cache import KVCache
+from .kv_cache import KV_FORMATS, KVCache
 from .modules import LLaMABlockCollection
 from .weights import Fp8Linear, PackedLinear
 
@@ -359,13 +359,43 @@ class LLaMAForCausalLM:
         return self.weight_bytes() - self.wte.numel() * 2
 
     # ------------------------------------------------------------------ cache
-    def init_cache(self, batch_size: int, max_length: int) -> KVCache:
-        """Reference ``init_cache(B, T)`` (``model.py:459-476``) without a dummy forward."""
+    KV_CACHE_FORMATS = KV_FORMATS
+
+    def _check_kv_format(self, fmt: str) -> str:
+        if fmt not in self.KV_CACHE_FORMATS:
+            raise ValueError(f"unknown KV-cache format {fmt!r} (one of {self.KV_CACHE_FORMATS})")
+        if fmt == "fp8_e4m3":
+            if self.head_dim != 128:
+                raise ValueError(f"the fp8_e4m3 KV cache needs head_dim == 128, got {self.head_dim}")
+            rep = self.n_heads // self.n_kv_heads
+            if self.n_heads % self.n_kv_heads or rep not in (1, 2, 4, 8):
+                raise ValueError("the fp8_e4m3 KV cache needs 1, 2, 4 or 8 query heads per kv head, got "
+                                 f"{self.n_heads} / {self.n_kv_heads}")
+        return fmt
+
+    def set_kv_cache_format(self, fmt: str) -> "LLaMAForCausalLM":
+        """The format of the KV caches this model creates from now on (``init_cache``, ``__call__``, ``score``,
+        ``generate``): ``"bf16"`` (the default) or ``"fp8_e4m3"`` -- K (post-RoPE) and V rows stored as e4m3 bytes with
+        one power-of-two scale per (row, kv head, slot), 132 bytes instead of 256 (``ops.Fp8KV``). The model then
+        computes what the bf16-cache model computes when every K / V row is replaced by its dequantised value at the
+        moment it is written. Runtime state: not written to checkpoints. ``ValueError`` for an unknown format, a head
+        dim other than 128, or a number of query heads per kv head outside {1, 2, 4, 8}."""
+        self._kv_cache_format = self._check_kv_format(fmt)
+        return self
+
+    @property
+    def kv_cache_format(self) -> str:
+        return getattr(self, "_kv_cache_format", "bf16")
+
+    def init_cache(self, batch_size: int, max_length: int, kv_format: Optional[str] = None) -> KVCache:
+        """Reference ``init_cache(B, T)`` (``model.py:459-476``) without a dummy forward. ``kv_format``: this cache's
+        format (default: the model's, ``set_kv_cache_format``)."""
         if max_length > self.rope_length:
             raise ValueError(f"max_length {max_length} exceeds the RoPE table ({self.rope_length}); "
                              "raise config.max_sequence_length")
+        fmt = self.kv_cache_format if kv_format is None else self._check_kv_format(kv_format)
         return KVCache(self.config.num_hidden_layers, batch_size, self.n_kv_heads, max_length,
-                       self.head_dim, self.device)
+                       self.head_dim, self.device, kv_format=fmt)
 
     # ------------------------------------------------------------------ core forward
     def _row_parallel(self, x: torch.Tensor, w: PackedLinear, h: torch.Tensor, hb: torch.Tensor,
@@ -454,7 +484,8 @@ class LLaMAForCausalLM:
             position_ids = torch.arange(s, dtype=torch.int32).expand(b, s)
         pos = _t(position_ids).to(self.device, torch.int32).reshape(b, s).contiguous()
         if past_key_values is None:
-            cache = KVCache(self.config.num_hidden_layers, b, self.n_kv_heads, s, self.head_dim, self.device)
+            cache = KVCache(self.config.num_hidden_layers, b, self.n_kv_heads, s, self.head_dim, self.device,
+                            kv_format=self.kv_cache_format)
             slot0 = 0
         else:
             cache = past_key_values
@@ -551,7 +582,8 @@ class LLaMAForCausalLM:
         parts = []
         for b0 in range(0, b, rows):
             b1 = min(b, b0 + rows)
-            cache = KVCache(self.config.num_hidden_layers, b1 - b0, self.n_kv_heads, s, self.head_dim, dev)
+            cache = KVCache(self.config.num_hidden_layers, b1 - b0, self.n_kv_heads, s, self.head_dim, dev,
+                            kv_format=self.kv_cache_format)
             km = key_mask[b0:b1] if key_mask is not None else None
             triple, *_ = self.forward_tokens(ids_d[b0:b1], pos_d[b0:b1].contiguous(), cache, 0, kv_start[b0:b1], km,
                                              logits_mode="logprob", targets=tgt_d[b0:b1].reshape(-1))

@@ -43,7 +43,7 @@ class LLaMAAttention:
         o_state = None
         if not output_attentions:
             # the o projection in the same launch where it fits (the 70B tensor-parallel shard at small batch)
-            og = ops.qkv_attention_o_groups(hb, lw.o, m.n_heads, m.n_kv_heads) if seq_len == 1 else 0
+            og = ops.qkv_attention_o_groups(hb, lw.o, m.n_heads, m.n_kv_heads, kc) if seq_len == 1 else 0
             o_state = m.comm.fused_o_state(hb, lw.o) if og else None
             og = og if o_state is not None else 0
             splits = ops.qkv_attention_splits(hb, lw.qkv, kc, seq_len, m.n_heads, m.n_kv_heads, key_mask, og)
@@ -72,7 +72,8 @@ class LLaMAAttention:
             # the layer output still comes from the attention kernel (as without the flag); the softmax weights the
             # reference returns (:277-286) are materialised beside it by the fp32 oracle, on the tensors' device
             s0 = int(slot0) if not torch.is_tensor(slot0) else int(slot0.item())
-            _, weights = ref.attention(q4, kc, vc, s0, kv_start, key_mask, return_weights=True)
+            kw, vw = (ops.kv8_dequant(kc, vc, s0 + seq_len) if ops.is_fp8_kv(kc) else (kc, vc))  # (an FP8 cache: its rows)
+            _, weights = ref.attention(q4, kw, vw, s0, kv_start, key_mask, return_weights=True)
             a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask)
         else:
             att_p = pk.att if pk is not None and ops.attention_packs(q4, kc, key_mask) else None

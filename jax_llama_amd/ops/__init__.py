@@ -22,6 +22,11 @@ from ._ext import ext
 
 BF16 = torch.bfloat16
 
+# One layer's K or V in the FP8 (e4m3) KV-cache format (ops/reference.py): accepted by rope_kv_write, linear_qkv_rope
+# and attention wherever they take a cache tensor
+Fp8KV = ref.Fp8KV
+is_fp8_kv = ref.is_fp8_kv
+
 # Linear epilogue modes (must match csrc/kernels/common.h)
 MODE_STORE = 0
 MODE_RESIDUAL = 1
@@ -473,6 +478,11 @@ def rope_kv_write(qkv: torch.Tensor, table: torch.Tensor, positions: torch.Tenso
     m = qkv.shape[0]
     q = torch.empty(m, n_heads, head_dim, dtype=BF16, device=qkv.device)
     slot_t = _slot_tensor(slot0, qkv.device)
+    if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):  # the quantising write (csrc/kernels/kv8.hip)
+        _check_kv8_pair(k_cache, v_cache)
+        ext().rope_kv_write_q8(qkv, table, positions.reshape(-1).to(torch.int32), k_cache.q, k_cache.scale, v_cache.q,
+                               v_cache.scale, slot_t, int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q)
+        return q
     ext().rope_kv_write(qkv, table, positions.reshape(-1).to(torch.int32), k_cache, v_cache,
                         slot_t, int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q)
     return q
@@ -491,6 +501,11 @@ def linear_qkv_rope(x: torch.Tensor, w, rms_eps: Optional[float], table: torch.T
                                    n_heads, n_kv_heads, head_dim)
     m = x.shape[0]
     e = ext()
+    if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
+        # FP8 KV cache: always a plain store and the quantising write kernel (the rows that get quantised are defined
+        # from the bf16 projection output; no RoPE epilogue quantises), bf16 and Fp8Linear weights alike
+        qkv = linear(x, w, rms_eps=rms_eps, x_packed=x_packed if m <= e.SKINNY_MAX_M else None)
+        return rope_kv_write(qkv, table, positions, k_cache, v_cache, slot0, seq_len, n_heads, n_kv_heads, head_dim)
     if is_fp8(w):
         if _w8_fast(e, x, w, MODE_QKV):
             q = torch.empty(m, n_heads, head_dim, dtype=BF16, device=x.device)
@@ -581,10 +596,10 @@ def _num_cus(device) -> int:
     return _CUS[key]
 
 
-def qkv_attention_o_groups(x: torch.Tensor, w_o, n_heads: int, n_kv_heads: int) -> int:
+def qkv_attention_o_groups(x: torch.Tensor, w_o, n_heads: int, n_kv_heads: int, k_cache=None) -> int:
     """Workgroups of the o projection when the fused decode launch can also run it (``linear_qkv_attention(o=...)``),
-    else 0."""
-    if not QKV_ATTN_O or not _is_gpu(x) or is_fp8(w_o):
+    else 0 (always 0 with an ``Fp8KV`` cache: the fused launch reads and writes bf16 caches only)."""
+    if not QKV_ATTN_O or not _is_gpu(x) or is_fp8(w_o) or is_fp8_kv(k_cache):
         return 0
     return int(ext().qkv_attn_o_groups(x.shape[0], n_heads // n_kv_heads, w_o.n, w_o.k))
 
@@ -596,6 +611,8 @@ def qkv_attention_splits(x: torch.Tensor, w, k_cache: torch.Tensor, seq_len: int
     once). ``o_groups``: the launch also holds the o projection's workgroups (``qkv_attention_o_groups``)."""
     if not QKV_ATTN or seq_len != 1 or key_mask is not None or not _is_gpu(x) or x.dtype != BF16 or is_fp8(w):
         return 0  # (an Fp8Linear: the fused launch reads bf16 fragments only)
+    if is_fp8_kv(k_cache):
+        return 0  # (an Fp8KV: the fused launch reads and writes bf16 caches only)
     m = x.shape[0]
     if QKV_ATTN == 1 and (m > 4 or n_heads < 8 * n_kv_heads):
         return 0
@@ -652,7 +669,7 @@ def attention_packs(q: torch.Tensor, k_cache: torch.Tensor, key_mask: Optional[t
     """Whether ``attention(..., out_packed=...)`` can write the packed copy for this decode shape: the ``packs`` of
     the launch's plan (csrc/kernels/attn_plan.h; it does not depend on how many key slots the launch covers)."""
     bsz, s, h, dh = q.shape
-    if s != 1:
+    if s != 1 or is_fp8_kv(k_cache):  # (the fp8-cache kernel writes no packed copy)
         return False
     rc, _why, _kernel, _nsplit, packs, *_ = ext().attn_decode_plan_check(
         bsz, h, k_cache.shape[1], dh, k_cache.shape[2], key_mask is not None)
@@ -675,6 +692,21 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
     slot_t = _slot_tensor(slot0, q.device)
     t_cap = int(max_kv) if max_kv is not None else k_cache.shape[2]
     e = ext()
+    if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
+        _check_kv8_pair(k_cache, v_cache)
+        if out_packed is not None:
+            raise ValueError("attention: no packed output copy with an Fp8KV cache (attention_packs)")
+        if s == 1:  # straight on the fp8 bytes (csrc/kernels/kv8.hip attn_decode_q8)
+            e.attn_decode_q8(q, k_cache.q, k_cache.scale, v_cache.q, v_cache.scale, slot_t, kv_start, key_mask, out,
+                             t_cap)
+        else:
+            # the rows the queries can see, dequantised (exact) into a scratch exactly that long: attn_prefill clamps
+            # the key rows it loads to its cache length, so it reads no scratch row that kv8_dequant did not write.
+            # A slot that lives on the device only (no host value without a sync): the whole cache.
+            n = k_cache.shape[2] if torch.is_tensor(slot0) else min(int(slot0) + s, k_cache.shape[2])
+            kd, vd = kv8_dequant(k_cache, v_cache, n, scratch=True)
+            e.attn_prefill(q, kd, vd, slot_t, kv_start, key_mask, out)
+        return out
     if s == 1:
         hkv = k_cache.shape[1]
         # one plan call (csrc/kernels/attn_plan.h): the split count and what the launch needs; a shape it refuses is
@@ -687,6 +719,30 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
     else:
         e.attn_prefill(q, k_cache, v_cache, slot_t, kv_start, key_mask, out)
     return out
+
+
+def _check_kv8_pair(k_cache, v_cache) -> None:
+    if not (is_fp8_kv(k_cache) and is_fp8_kv(v_cache)):
+        raise TypeError("FP8 KV cache: K and V must both be Fp8KV")
+
+
+def kv8_dequant(k_cache: "Fp8KV", v_cache: "Fp8KV", n: Optional[int] = None, scratch: bool = False):
+    """Slots ``[0, n)`` (default: all) of an ``Fp8KV`` pair as bf16 ``[B, Hkv, n, 128]`` tensors ``(k, v)``:
+    ``q * scale``, exact. ``scratch``: the results live in the workspace (valid until the next such call)."""
+    _check_kv8_pair(k_cache, v_cache)
+    b, hkv, t, dh = k_cache.shape
+    n = t if n is None else int(n)
+    if not _is_gpu(k_cache.q):
+        return k_cache.dequant(n), v_cache.dequant(n)
+    numel = b * hkv * n * dh
+    if scratch:
+        kd = workspace.get("kv8_k", numel, BF16, k_cache.device).view(b, hkv, n, dh)
+        vd = workspace.get("kv8_v", numel, BF16, k_cache.device).view(b, hkv, n, dh)
+    else:
+        kd = torch.empty(b, hkv, n, dh, dtype=BF16, device=k_cache.device)
+        vd = torch.empty_like(kd)
+    ext().kv8_dequant(k_cache.q, k_cache.scale, v_cache.q, v_cache.scale, n, kd, vd)
+    return kd, vd
 
 
 def _slot_tensor(slot0, device):

@@ -91,6 +91,75 @@ def dequantize_fp8_rows(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return (q.float() * scale.float()[:, None]).to(BF16)
 
 
+KV8_DH = 128  # the head dim of the FP8 KV cache (the attention kernels' only head dim)
+
+
+class Fp8KV:
+    """One layer's K (post-RoPE) or V in the FP8 KV-cache format. A *row* is the 128 values of one (batch row, kv
+    head, slot), quantised by ``quantize_fp8_rows``: ``q`` uint8 ``[B, Hkv, T, 128]`` holds the e4m3fn bytes in natural
+    element order (``q.view(torch.float8_e4m3fn)`` is readable), ``scale`` fp32 ``[B, Hkv, T]`` the power-of-two row
+    scales. 132 bytes per row instead of bf16's 256. Unwritten slots are bytes 0 and scale 0 (they dequantise to 0).
+    Accepted wherever ``rope_kv_write`` / ``linear_qkv_rope`` / ``attention`` take a cache tensor; the model then
+    computes what the bf16 model computes when every K / V row is replaced by ``q * scale`` (exact in bf16) at the
+    moment it is written."""
+
+    __slots__ = ("q", "scale")
+
+    def __init__(self, q: torch.Tensor, scale: torch.Tensor):
+        if q.dtype != torch.uint8 or q.dim() != 4 or q.shape[-1] != KV8_DH:
+            raise ValueError(f"Fp8KV: q must be uint8 [B, Hkv, T, {KV8_DH}], got {q.dtype} {tuple(q.shape)}")
+        if scale.dtype != torch.float32 or tuple(scale.shape) != tuple(q.shape[:3]) or scale.device != q.device:
+            raise ValueError(f"Fp8KV: scale must be fp32 {tuple(q.shape[:3])} on {q.device}, got {scale.dtype} "
+                             f"{tuple(scale.shape)} on {scale.device}")
+        self.q, self.scale = q, scale
+
+    @classmethod
+    def zeros(cls, batch: int, n_kv_heads: int, max_length: int, device="cpu") -> "Fp8KV":
+        return cls(torch.zeros(batch, n_kv_heads, max_length, KV8_DH, dtype=torch.uint8, device=device),
+                   torch.zeros(batch, n_kv_heads, max_length, dtype=torch.float32, device=device))
+
+    @property
+    def shape(self):
+        return self.q.shape
+
+    @property
+    def device(self):
+        return self.q.device
+
+    def nbytes(self) -> int:
+        return self.q.numel() + 4 * self.scale.numel()
+
+    def dequant(self, n: Optional[int] = None) -> torch.Tensor:
+        """Slots ``[0, n)`` (default: all) as bf16 ``[B, Hkv, n, 128]``: ``q * scale``, exact."""
+        n = self.q.shape[2] if n is None else n
+        return (self.q[:, :, :n].view(FP8).float() * self.scale[:, :, :n, None]).to(BF16)
+
+    def store(self, rows: torch.Tensor, slot0: int) -> None:
+        """Quantise bf16 rows ``[B, Hkv, S, 128]`` into slots ``slot0 .. slot0 + S - 1``."""
+        b, hkv, s, dh = rows.shape
+        q, scale = quantize_fp8_rows(rows.to(BF16).reshape(-1, dh))
+        self.q[:, :, slot0:slot0 + s] = q.view(torch.uint8).reshape(b, hkv, s, dh)
+        self.scale[:, :, slot0:slot0 + s] = scale.reshape(b, hkv, s)
+
+    def zero_(self) -> "Fp8KV":
+        self.q.zero_()
+        self.scale.zero_()
+        return self
+
+
+def is_fp8_kv(cache) -> bool:
+    return isinstance(cache, Fp8KV)
+
+
+def _kv_store(cache, rows: torch.Tensor, slot0: int) -> None:
+    """``rows [B, Hkv, S, Dh]`` into cache slots ``slot0 ..``: a cast for a tensor cache, a quantising store of the
+    bf16 rows for an ``Fp8KV``."""
+    if is_fp8_kv(cache):
+        cache.store(rows, slot0)
+    else:
+        cache[:, :, slot0:slot0 + rows.shape[2]] = rows.to(cache.dtype)
+
+
 def _check_fp8_shape(n: int, k: int):
     if n <= 0 or k <= 0 or n % 16 or k % 64:
         raise ValueError(f"FP8 linear weights need N % 16 == 0 and K % 64 == 0, got {n}x{k}")
@@ -227,14 +296,19 @@ def rope_kv_write(qkv, table, positions, k_cache, v_cache, slot0: int, seq_len: 
     kr = apply_rope(k, table, positions).to(BF16)
     kr = kr.reshape(b, seq_len, n_kv_heads, head_dim).permute(0, 2, 1, 3)
     vv = v.reshape(b, seq_len, n_kv_heads, head_dim).permute(0, 2, 1, 3)
-    k_cache[:, :, slot0:slot0 + seq_len] = kr.to(k_cache.dtype)
-    v_cache[:, :, slot0:slot0 + seq_len] = vv.to(v_cache.dtype)
+    _kv_store(k_cache, kr, slot0)  # (an Fp8KV: the bf16 rows, quantised)
+    _kv_store(v_cache, vv, slot0)
     return qr
 
 
 def linear_qkv_rope(x, w_dense, rms_eps, table, positions, k_cache, v_cache, slot0: int, seq_len: int,
                     n_heads: int, n_kv_heads: int, head_dim: int) -> torch.Tensor:
-    """Fused-kernel rounding points: fp32 projection -> fp32 RoPE -> one bf16 rounding."""
+    """Fused-kernel rounding points: fp32 projection -> fp32 RoPE -> one bf16 rounding. With ``Fp8KV`` caches the
+    projection is a plain bf16 store followed by ``rope_kv_write`` (the rows that get quantised are defined from the
+    bf16 projection output)."""
+    if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
+        return rope_kv_write(linear(x, w_dense, rms_eps), table, positions, k_cache, v_cache, slot0, seq_len,
+                             n_heads, n_kv_heads, head_dim)
     y = _mm(x, w_dense, rms_eps)  # fp32 [M, (H+2Hkv)*Dh]
     m = y.shape[0]
     b = m // seq_len
@@ -257,11 +331,16 @@ def attention(q, k_cache, v_cache, slot0: int, kv_start: torch.Tensor,
     """q: [B, S, H, Dh] (already rotated) for cache slots ``slot0+s``; caches
     ``[B, Hkv, T, Dh]``. Query at slot i attends keys j with ``kv_start[b] <= j <= i`` and
     ``key_mask[b, j]`` (if given). Rows with no valid key produce 0. Returns
-    ``[B, S, H*Dh]`` bf16 (and fp32 weights ``[B, H, S, slot0+S]`` if requested)."""
+    ``[B, S, H*Dh]`` bf16 (and fp32 weights ``[B, H, S, slot0+S]`` if requested). ``Fp8KV`` caches are read through
+    their dequantised rows (q is never quantised)."""
     bsz, s, h, dh = q.shape
+    t_len = slot0 + s
+    if is_fp8_kv(k_cache):
+        k_cache = k_cache.dequant(t_len)
+    if is_fp8_kv(v_cache):
+        v_cache = v_cache.dequant(t_len)
     hkv = k_cache.shape[1]
     rep = h // hkv
-    t_len = slot0 + s
     k = k_cache[:, :, :t_len].float().repeat_interleave(rep, dim=1)  # [B,H,T,Dh]
     v = v_cache[:, :, :t_len].float().repeat_interleave(rep, dim=1)
     qf = q.float().permute(0, 2, 1, 3)  # [B,H,S,Dh]

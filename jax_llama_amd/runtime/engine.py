@@ -32,6 +32,7 @@ from typing import Optional
 import torch
 
 from .. import ops
+from ..models.kv_cache import kv_row_bytes
 from ..ops import reference as ref
 
 _NEG_INF = float("-inf")
@@ -306,8 +307,7 @@ class DecodeEngine:
             # a failed step (a peer or in-launch timeout, an error mid-decode) can leave non-finite rows in this
             # engine's cache beyond where the next prompt writes; the kernels mask keys past the valid length by
             # probability 0, and 0 x NaN is NaN: zero the cache so the next call starts as from a fresh engine
-            self.cache.k.zero_()
-            self.cache.v.zero_()
+            self.cache.zero_()
             raise
         finally:
             if rng_saved is not None:
@@ -351,13 +351,16 @@ def _engine_budget(model) -> int:
 
 def get_engine(model, batch_size: int, max_length: int) -> DecodeEngine:
     """Per-(model, B, max_length) engines (each owns a KV cache and a captured decode graph), kept in
-    LRU order and bounded by the bytes of their KV caches."""
-    key = (id(model), batch_size, max_length)
+    LRU order and bounded by the bytes of their KV caches. The model's KV-cache format is part of the key: an engine
+    owns a cache of one format."""
+    fmt = getattr(model, "kv_cache_format", "bf16")
+    key = (id(model), batch_size, max_length, fmt)
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)
         return eng
-    need = model.config.num_hidden_layers * 2 * batch_size * model.n_kv_heads * max_length * model.head_dim * 2
+    need = (model.config.num_hidden_layers * 2 * batch_size * model.n_kv_heads * max_length *
+            kv_row_bytes(fmt, model.head_dim))
     budget = _engine_budget(model)
     held = sum(e.cache.nbytes() for e in _ENGINES.values())
     while _ENGINES and held + need > budget:

@@ -9,6 +9,13 @@ impl (ext.attn_set_impl / attn_set_v3_max_pairs): 2 = default dispatch; 3 = v3 (
 5 = split small-batch kernel (v5) where it applies; 6 = v5 with the first merge (4 splits per load round);
 7 = v4 (register ring, one split) forced; 9 = v2 (LDS-DMA ring, KPG 4, 2 slots) forced; 60 = v6 (matrix cores),
 61 / 62 / 64 / 68 = v6 with 1 / 2 / 4 / 8 waves per (row, kv head) pair. Prints one JSON line per (shape, impl).
+
+  python tools/bench_attn_decode.py --shapes 64x384 2048x384 --impls 2 --kv bf16 fp8 --q8-waves 0 1 8
+
+--kv fp8: the FP8 (e4m3) KV cache's kernel (csrc/kernels/kv8.hip) on a cache of random codes, beside the bf16 kernels on
+the bf16 cache that holds the same (dequantised) values, alternating in one process; --q8-waves pins its waves per pair
+(0: the plan's choice). Every record carries the median and the minimum over the rounds and GB/s (the valid K / V bytes
+of the format, scales included, over the median).
 """
 from __future__ import annotations
 
@@ -52,6 +59,8 @@ def main():
     ap.add_argument("--impls", type=int, nargs="+", default=[2, 1])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"])
+    ap.add_argument("--q8-waves", type=int, nargs="+", default=[0], help="fp8: waves per pair pinned (0: by shape)")
     args = ap.parse_args()
     e = ops.ext()
     cfg = get_preset(args.model)
@@ -61,16 +70,34 @@ def main():
         b, t = (int(v) for v in shape.split("x"))
         tc = max(args.cache_len, t)
         g = torch.Generator(device="cuda").manual_seed(b * 7 + t)
-        kc = torch.randn(b, hkv, tc, hd, device="cuda", generator=g).to(torch.bfloat16)
-        vc = torch.randn(b, hkv, tc, hd, device="cuda", generator=g).to(torch.bfloat16)
+        k8 = v8 = None
+        if "fp8" in args.kv:
+            # random finite e4m3 codes (0x7F / 0xFF are NaN) at row scales 2^-9 .. 2^-7; the bf16 caches hold q * scale
+            def codes():
+                c = torch.randint(0, 0x7F, (b, hkv, tc, hd), device="cuda", generator=g, dtype=torch.uint8)
+                return c + 0x80 * torch.randint(0, 2, c.shape, device="cuda", generator=g, dtype=torch.uint8)
+
+            def scales():
+                return 2.0 ** torch.randint(-9, -6, (b, hkv, tc), device="cuda", generator=g).float()
+
+            k8, v8 = ops.Fp8KV(codes(), scales()), ops.Fp8KV(codes(), scales())
+            kc, vc = ops.kv8_dequant(k8, v8)
+        else:
+            kc = torch.randn(b, hkv, tc, hd, device="cuda", generator=g).to(torch.bfloat16)
+            vc = torch.randn(b, hkv, tc, hd, device="cuda", generator=g).to(torch.bfloat16)
         q = torch.randn(b, 1, h, hd, device="cuda", generator=g).to(torch.bfloat16)
         slot = torch.tensor([t - 1], dtype=torch.int32, device="cuda")
         ks = torch.zeros(b, dtype=torch.int32, device="cuda")
         res, first = {}, None
         graphs = {}
-        for impl in args.impls:
-            set_impl(e, impl)
-            out = ops.attention(q, kc, vc, slot, ks)  # sizes the workspaces before capture
+        runs = [("bf16", i) for i in args.impls if "bf16" in args.kv] + [("fp8", w) for w in args.q8_waves if k8]
+        for run in runs:
+            kv, impl = run
+            set_impl(e, impl if kv == "bf16" else 2)
+            if kv == "fp8":
+                e.attn_set_q8_waves(impl)
+            ck, cv = (kc, vc) if kv == "bf16" else (k8, v8)
+            out = ops.attention(q, ck, cv, slot, ks)  # sizes the workspaces before capture
             torch.cuda.synchronize()
             first = out.float() if first is None else first
             diff = float((out.float() - first).abs().max())
@@ -78,18 +105,19 @@ def main():
             with torch.cuda.graph(ga):
                 for _ in range(args.reps):
                     flush.fill_(1)
-                    ops.attention(q, kc, vc, slot, ks)
+                    ops.attention(q, ck, cv, slot, ks)
             with torch.cuda.graph(gf):
                 for _ in range(args.reps):
                     flush.fill_(1)
-            graphs[impl] = (ga, gf, diff)
+            waves = e.attn_decode_q8_plan_check(b, h, hkv, hd, tc, False)[2] if kv == "fp8" else None
+            graphs[run] = (ga, gf, diff, waves)
         e.attn_set_v6_diag(0)
         e.attn_reset_knobs()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        best = {impl: float("inf") for impl in args.impls}
+        times = {run: [] for run in runs}
         for _ in range(args.rounds):
-            for impl in args.impls:
-                ga, gf, _ = graphs[impl]
+            for run in runs:
+                ga, gf, _, _ = graphs[run]
                 tt = []
                 for gr in (ga, gf):
                     gr.replay()
@@ -98,12 +126,18 @@ def main():
                     ev1.record()
                     ev1.synchronize()
                     tt.append(ev0.elapsed_time(ev1))
-                best[impl] = min(best[impl], (tt[0] - tt[1]) * 1000.0 / args.reps)
-        for impl in args.impls:
+                times[run].append((tt[0] - tt[1]) * 1000.0 / args.reps)
+        for run in runs:
+            kv, impl = run
+            ts = sorted(times[run])
+            med = ts[len(ts) // 2]
+            nbytes = b * hkv * t * 2 * (hd + 4 if kv == "fp8" else 2 * hd)  # the valid K and V rows of the format
             res = {"op": "attn_decode_graph", "model": args.model, "tp": args.tp, "b": b, "t": t, "cache_len": tc,
-                   "impl": impl, "us": round(best[impl], 2), "max_diff_vs_first": round(graphs[impl][2], 5)}
+                   "kv": kv, "impl": impl if kv == "bf16" else None, "q8_waves": graphs[run][3],
+                   "us": round(ts[0], 2), "us_median": round(med, 2), "kv_bytes": nbytes,
+                   "gbps": round(nbytes / med / 1e3, 1), "max_diff_vs_first": round(graphs[run][2], 5)}
             print(json.dumps(res), flush=True)
-        del graphs, kc, vc
+        del graphs, kc, vc, k8, v8
 
 
 if __name__ == "__main__":

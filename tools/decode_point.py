@@ -27,7 +27,10 @@ def main():
     ap.add_argument("--weights", nargs="+", choices=["bf16", "fp8"], default=["bf16"],
                     help="fp8: the layer projections quantised to FP8 e4m3 (LLaMAForCausalLM.quantize_weights_); "
                     "`bf16 fp8`: one model of each in this process, measured alternately per point")
-    ap.add_argument("--reps", type=int, default=1, help="repeats of every point (alternating over --weights)")
+    ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"],
+                    help="KV-cache format (LLaMAForCausalLM.set_kv_cache_format; fp8: e4m3 rows with power-of-two "
+                    "scales); `bf16 fp8`: the same model with each, measured alternately per point")
+    ap.add_argument("--reps", type=int, default=1, help="repeats of every point (alternating over --weights and --kv)")
     ap.add_argument("--tune-report", action="store_true", help="print the decode-kernel choices and the graph-timed "
                     "microseconds of every candidate measured (ops/autotune.py)")
     args = ap.parse_args()
@@ -47,11 +50,17 @@ def main():
             models[wf].quantize_weights_("fp8_e4m3")
     for b in args.batch:
         for rep in range(args.reps):
-            for wf, m in models.items():
+            for wf, kv in ((wf, kv) for wf in models for kv in args.kv):
+                m = models[wf]
+                m.set_kv_cache_format("fp8_e4m3" if kv == "fp8" else "bf16")
                 r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample)
                 r["model"] = args.model
                 r["mp"] = args.tp_proxy
                 r["weights"] = wf
+                r["kv"] = kv
+                r["kv_cache_gb"] = round(m.config.num_hidden_layers * 2 * b * m.n_kv_heads *
+                                         (args.prompt_len + args.gen_len) *
+                                         (m.head_dim + 4 if kv == "fp8" else 2 * m.head_dim) / 1e9, 2)
                 r["rep"] = rep
                 r["fused_row_parallel"] = comm is not None and comm.fused is not None
                 r["hbm_roofline_ms"] = round(m.streamed_weight_bytes_per_token() / 6.29e12 * 1e3, 4)
