@@ -626,7 +626,8 @@ void kv8_dequant(Tensor kq, Tensor ks, Tensor vq, Tensor vs, int64_t n, Tensor k
 }
 
 void attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor slot, Tensor kv_start,
-                    c10::optional<Tensor> key_mask, Tensor out, int64_t t_cap) {
+                    c10::optional<Tensor> key_mask, Tensor out, int64_t t_cap, c10::optional<Tensor> ws,
+                    c10::optional<Tensor> tickets) {
   for (auto* t : {&q, &slot, &kv_start, &out}) check_gpu(*t, "attn_decode_q8 arg");
   check(q.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16 && q.dim() == 4 && q.size(1) == 1,
         "attn_decode_q8: q bf16 [B, 1, H, Dh]");
@@ -648,11 +649,30 @@ void attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor
   const jla::AttnQ8PlanResult r =
       jla::attn_decode_q8_plan(jla::attn_knobs(), b, h, hkv, dh, t_cap, key_mask.has_value());
   TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: attn_decode_q8: no plan (", r.why, "; see attn_plan.h)");
+  // a plan with key splits needs its workspace and tickets (attn_decode_q8_split_check); an unsplit one takes none
+  float* wsp = nullptr;
+  int32_t* tkp = nullptr;
+  if (r.plan.nsplit > 1) {
+    TORCH_CHECK(ws.has_value() && tickets.has_value(), "jax_llama_amd._C: attn_decode_q8: the plan splits the keys (nsplit ",
+                r.plan.nsplit, "): ws and tickets are required (attn_decode_q8_split_check)");
+    check_gpu(*ws, "ws");
+    check_gpu(*tickets, "tickets");
+    TORCH_CHECK(ws->scalar_type() == torch::kFloat32 && ws->device() == q.device() &&
+                    (size_t)ws->numel() >= r.plan.ws_floats,
+                "jax_llama_amd._C: attn_decode_q8: ws must be fp32 on q's device with at least B * H * nsplit * (128 + 4) = ",
+                r.plan.ws_floats, " floats (attn_decode_q8_split_check)");
+    TORCH_CHECK(tickets->scalar_type() == torch::kInt32 && tickets->device() == q.device() &&
+                    tickets->numel() >= r.plan.tickets,
+                "jax_llama_amd._C: attn_decode_q8: tickets must be int32 on q's device, one per (row, kv head) pair = ",
+                r.plan.tickets, " (attn_decode_q8_split_check)");
+    wsp = ptr<float>(*ws);
+    tkp = ptr<int32_t>(*tickets);
+  }
   const uint8_t* km = key_mask.has_value() ? ptr<uint8_t>(*key_mask) : nullptr;
   const int ml = key_mask.has_value() ? key_mask->size(1) : 0;
   rc(jla::attn_decode_q8(cbf(q), ptr<uint8_t>(kq), ptr<float>(ks), ptr<uint8_t>(vq), ptr<float>(vs),
                          ptr<int32_t>(slot), ptr<int32_t>(kv_start), km, ml, bf(out), b, h, hkv, dh, T, t_cap,
-                         stream()),
+                         stream(), wsp, r.plan.ws_floats, tkp, r.plan.tickets),
      "attn_decode_q8");
 }
 
@@ -1150,7 +1170,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("kv8_dequant", &kv8_dequant, py::arg("kq"), py::arg("ks"), py::arg("vq"), py::arg("vs"), py::arg("n"),
         py::arg("kout"), py::arg("vout"));
   m.def("attn_decode_q8", &attn_decode_q8, py::arg("q"), py::arg("kq"), py::arg("ks"), py::arg("vq"), py::arg("vs"),
-        py::arg("slot"), py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"), py::arg("t_cap"));
+        py::arg("slot"), py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"), py::arg("t_cap"),
+        py::arg("ws") = py::none(), py::arg("tickets") = py::none());
   // (rc, why, waves, kpg, rep) of the fp8-cache decode-attention launch under the current knobs (kernels/attn_plan.h)
   m.def("attn_decode_q8_plan_check", [](int64_t b, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap, bool masked) {
     const jla::AttnQ8PlanResult r =
@@ -1159,6 +1180,29 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"));
   m.def("attn_set_q8_waves", [](int64_t w) { jla::attn_set_q8_waves((int)w); },
         "waves per pair of the fp8-cache decode attention pinned to 1 / 8 (tests, A/B); 0: by shape");
+  // (rc, why, nsplit, ws_floats, tickets) of the same plan: the key splits and what a split launch must be given
+  m.def("attn_decode_q8_split_check", [](int64_t b, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap, bool masked) {
+    const jla::AttnQ8PlanResult r =
+        jla::attn_decode_q8_plan(jla::attn_knobs(), (int)b, (int)h, (int)hkv, (int)dh, (int)t_cap, masked);
+    return py::make_tuple(r.rc, r.why, r.plan.nsplit, (int64_t)r.plan.ws_floats, r.plan.tickets);
+  }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"));
+  m.def("attn_set_q8_splits", [](int64_t n) { jla::attn_set_q8_splits((int)n); },
+        "key splits per pair of the fp8-cache decode attention: 0 by shape, 1 never, n > 1 pinned (tests, A/B)");
+  // (n_act, [(key_begin, key_end) per split]) of the valid keys [lo, hi) at kpg key rows per lane group: the geometry
+  // function the 8-wave kernel calls (kernels/attn_plan.h attn_q8_split_range), on the host
+  m.def("attn_q8_split_ranges", [](int64_t lo, int64_t hi, int64_t kpg, int64_t nsplit) {
+    check(kpg >= 1 && kpg <= 8 && nsplit >= 1 && lo <= INT32_MAX && hi <= INT32_MAX && lo >= INT32_MIN &&
+              hi >= INT32_MIN && nsplit <= INT32_MAX,
+          "attn_q8_split_ranges: kpg in 1..8, nsplit >= 1, int32 keys");
+    std::vector<std::pair<int, int>> ranges;
+    int n_act = 0;
+    for (int s = 0; s < (int)nsplit; ++s) {
+      const jla::AttnQ8SplitRange r = jla::attn_q8_split_range((int)lo, (int)hi, 32 * (int)kpg, (int)nsplit, s);
+      n_act = r.n_act;
+      ranges.emplace_back(r.key_begin, r.key_end);
+    }
+    return py::make_tuple(n_act, ranges);
+  }, py::arg("lo"), py::arg("hi"), py::arg("kpg"), py::arg("nsplit"));
   m.def("argmax", &argmax);
   m.def("topk_chunks", [](int64_t v) { return jla::topk_chunks(v); });
   m.def("car_alloc", &car_alloc);

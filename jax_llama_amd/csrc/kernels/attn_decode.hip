@@ -834,6 +834,7 @@ void attn_set_v5_fold(int n) { g_attn_knobs.v5_fold = (n == 4 || n == 12) ? n : 
 void attn_set_v6(int mode) { g_attn_knobs.v6_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
 void attn_set_v6_wpp(int wpp) { g_attn_knobs.v6_wpp = (wpp == 1 || wpp == 2 || wpp == 4 || wpp == 8) ? wpp : 0; }
 void attn_set_q8_waves(int waves) { g_attn_knobs.q8_waves = (waves == 1 || waves == 8) ? waves : 0; }
+void attn_set_q8_splits(int n) { g_attn_knobs.q8_splits = n > 0 ? n : 0; }
 
 // Launches the kernel attn_decode_plan() names: each JLA_AD* row below maps plan fields to one instantiation (a plan
 // no row matches would be a bug in the plan: -1). -2: nsplit is not the plan's; -3: a packed copy this launch cannot

@@ -29,6 +29,7 @@ struct AttnKnobs {
   bool v4 = true;           // the register-ring stream (v4); impl 4 turns it off (v2 everywhere v4 would run)
   bool v2_kpg4 = false;     // impl 4: v2's (KPG 4, 2 slots) ring at rep <= 4 for every size, not only from 16384 pairs
   int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8; 0 = by shape
+  int q8_splits = 0;        // ... its key splits per pair: 0 = by shape, 1 = never, n > 1 pinned (clamped to the chunks of t_cap)
 };
 
 enum AttnKernel { ATTN_V2 = 2, ATTN_V3, ATTN_V4, ATTN_V5, ATTN_V6 };
@@ -159,28 +160,70 @@ inline AttnPlanResult attn_decode_plan(const AttnKnobs& k, int B, int H, int Hkv
   return {0, "", p};
 }
 
-// ---- the FP8 (e4m3) KV cache (kv8.hip): one kernel template, attn_decode_q8_kernel, one workgroup per (row, kv head)
-// pair straight on the fp8 bytes; no key splits, no workspace, no tickets, no packed copy. Every rule of that launch:
+// ---- the FP8 (e4m3) KV cache (kv8.hip): one kernel template, attn_decode_q8_kernel, straight on the fp8 bytes: one
+// workgroup per (row, kv head) pair, or -- few pairs with a long context -- one per (pair, key split) with a
+// last-arriver merge; no packed copy. Every rule of that launch:
 constexpr int ATTN_Q8_ONE_WAVE_MIN_PAIRS = 2048;  // one wave per pair from here (B = 256 at 8 kv heads); see the rule
+constexpr int ATTN_Q8_SPLIT_WGS = 256;            // key splits until pairs x splits reaches this many workgroups ...
+constexpr int ATTN_Q8_SPLIT_MIN_CHUNKS = 4;       // ... of at least this many chunks of t_cap each; see the rule
+constexpr int ATTN_Q8_MAX_SPLITS = 64;            // what a pinned count is cut to (the merge is one workgroup's)
 struct AttnQ8Plan {
-  int rep;    // query heads per kv head
-  int waves;  // waves per pair: 8 (v3's structure) or 1 (large batches, as v4 serves them for bf16)
-  int kpg;    // key rows per lane group per chunk
+  int rep;     // query heads per kv head
+  int waves;   // waves per pair: 8 (v3's structure) or 1 (large batches, as v4 serves them for bf16)
+  int kpg;     // key rows per lane group per chunk
+  int nsplit;  // key splits per pair (1: the unsplit launch, no workspace); only with 8 waves
+  size_t ws_floats;  // nsplit > 1: the launch is given this many floats, [m, l, 0, 0, o[128]] per head and split ...
+  int tickets;       // ... and this many zero-initialised int32 tickets, one per pair (self-resetting); 0 / 0 unsplit
 };
 struct AttnQ8PlanResult {
   int rc;           // 0 legal; -1 not
   const char* why;  // the rule that refused the call
   AttnQ8Plan plan;
 };
+
+#if defined(__HIPCC__)
+#define JLA_PLAN_HD __host__ __device__
+#else
+#define JLA_PLAN_HD
+#endif
+// The keys of one split of the 8-wave kernel. The valid keys [lo, hi) of a pair are device state (kv_start, the slot),
+// so the splits cut them, not the cache: the chunks (ch = 32 kpg keys, aligned to multiples of ch as the unsplit
+// stream's are) from the one that holds lo to the one that holds hi - 1 are dealt out per = ceil(chunks / nsplit) at a
+// time, split s takes chunks [s per, min((s + 1) per, chunks)), and n_act = ceil(chunks / per) <= nsplit splits get
+// any. A split with s >= n_act has no keys; lo >= hi gives n_act = 0. Called by the kernel (every workgroup of a pair
+// computes the same n_act: it is what the ticket counts to) and, through attn_q8_split_ranges, by the tests.
+struct AttnQ8SplitRange {
+  int n_act;      // the splits of this pair that hold keys
+  int c_begin;    // the first chunk's first key, a multiple of ch (<= key_begin)
+  int key_begin;  // the split's keys [key_begin, key_end), within [lo, hi); empty for s >= n_act
+  int key_end;
+};
+JLA_PLAN_HD inline AttnQ8SplitRange attn_q8_split_range(int lo, int hi, int ch, int nsplit, int s) {
+  AttnQ8SplitRange r{0, 0, 0, 0};
+  if (lo < 0) lo = 0;
+  if (lo >= hi || ch < 1 || nsplit < 1) return r;
+  const int first = lo - lo % ch;
+  const int chunks = (hi - first + ch - 1) / ch;
+  const int per = (chunks + nsplit - 1) / nsplit;
+  r.n_act = (chunks + per - 1) / per;
+  if (s < 0 || s >= r.n_act) return r;
+  const int c0 = s * per, c1 = (s + 1) * per < chunks ? (s + 1) * per : chunks;
+  r.c_begin = first + c0 * ch;
+  r.key_begin = r.c_begin > lo ? r.c_begin : lo;
+  r.key_end = hi - first > c1 * ch ? first + c1 * ch : hi;  // (no first + c1 ch past hi: no overflow near INT_MAX)
+  return r;
+}
+
 inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, int Hkv, int Dh, int t_cap, bool masked) {
   const auto fail = [](const char* why) { return AttnQ8PlanResult{-1, why, AttnQ8Plan{}}; };
-  (void)t_cap, (void)masked;  // no rule depends on them yet (no key splits; both wave forms take a key mask)
+  (void)masked;  // no rule depends on it (both wave forms and the split form take a key mask)
   if (Dh != ATTN_DH) return fail("head dim: Dh == 128");
   if (H < 1 || Hkv < 1 || H % Hkv) return fail("GQA: H a positive multiple of Hkv");
   const int rep = H / Hkv, pairs = B * Hkv;
   if (rep > 8 || (rep & (rep - 1))) return fail("fp8 KV cache: query heads per kv head 1, 2, 4 or 8");
+  if (k.q8_splits > 1 && k.q8_waves == 1) return fail("fp8 KV cache: key splits (q8_splits > 1) only with 8 waves per pair");
   AttnQ8Plan p{};
-  p.rep = rep;
+  p.rep = rep, p.nsplit = 1;
   // One wave per pair from 2048 pairs, 8 waves below. The rule started as the bf16 plan's v3 / v4 boundary (1 wave where
   // rep <= 4 && B > 32, or from 4096 pairs) and moved on these records (profiles/kv8_attn_decode_ab.jsonl; graph-timed,
   // cold K / V, medians of 7 rounds, us at 8 waves / 1 wave), T = 384 unless noted:
@@ -189,10 +232,48 @@ inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, in
   //                                   B = 64 at T = 8192: 318 / 659
   //   rep 8 (Llama-3-70B, 8 kv heads) B = 32: 19.7 / 65.6   B = 256: 143.5 / 102.6
   // so 512 and 1024 pairs (where the old rule ran 1 wave at rep 4) stay with 8 waves, and rep 8 at 2048 pairs (where it
-  // ran 8) takes 1. Few pairs with a long context want the 8 waves all the more; a lone pair still runs on one CU.
+  // ran 8) takes 1. Few pairs with a long context want the 8 waves all the more, and key splits (below).
   p.waves = k.q8_waves ? k.q8_waves : (pairs >= ATTN_Q8_ONE_WAVE_MIN_PAIRS ? 1 : 8);
   // 16 scores per query-head set and lane group at most (rep x KPG <= 16, the v3 bound: no spills), 8 rows at most
   p.kpg = rep <= 2 ? 8 : 16 / rep;
+  // ---- key splits, 8 waves only (the 1-wave form is for pairs that fill the chip on their own). An unsplit pair
+  // streams on one CU, so below one workgroup per CU the launch takes the time of one pair's whole context. By shape:
+  // enough splits for ATTN_Q8_SPLIT_WGS workgroups, each at least ATTN_Q8_SPLIT_MIN_CHUNKS chunks of t_cap so that a
+  // split's stream outlasts the merge it causes. Both constants on these records (profiles/kv8_attn_decode_split_ab.jsonl;
+  // graph-timed, cold K / V, medians of 7 rounds, us; "u" unsplit, then pinned counts, "*" the rule's), cache full:
+  //   rep 4 (Llama-3-8B, 8 kv heads), T = 8192
+  //     B = 1:  u 121.8   2: 66.7   4: 36.9   8: 22.8   16*: 18.4   32: 20.5     (bf16 plan: 40.3)
+  //     B = 4:  u 126.9   2: 72.3   4: 41.6   8*: 34.0   16: 39.4   32: 50.1     (84.6)
+  //     B = 16: u 128.3   2*: 107.3   4: 107.2   8: 118.9   16: 123.0            (161.8)
+  //     B = 64: u 290.2   2: 302.4   4: 318.2                                    (568.4)  512 pairs: unsplit
+  //   T = 32768   B = 1: u 476.5   8: 73.3   16: 43.6   32*: 38.5   B = 4: u 477.8   4: 132.5   8*: 108.3   16: 110.3
+  //               B = 16: u 484.6   2*: 284.6   4: 289.4           B = 64: u 1062   2: 1076
+  //   T = 384     B = 1: u 10.1   2: 10.8   3: 8.8   B = 4: u 10.4   2: 11.4   3: 9.7 (the rounds overlap)
+  //               B = 16: u 11.3   2: 13.1   3: 16.9   B = 64: u 28.3   2: 41.0          -> under 4 chunks: unsplit
+  //   rep 8 (Llama-3-70B, 8 kv heads), T = 8192   B = 1: u 250.5   8: 40.9   16: 28.3   32*: 26.0   (125.7)
+  //                                               B = 8: u 252.1   2: 132.8   4*: 76.2   8: 86.6    (292.8)
+  // and with the slot at T / 8 of a T = 8192 cache (the splits cut the valid keys): rep 4 B = 1 u 19.0 -> 10.5,
+  // B = 4 20.8 -> 13.5, B = 16 20.7 -> 18.9; rep 8 B = 1 37.3 -> 15.5, B = 8 38.0 -> 21.2. So one workgroup per CU is
+  // the count to aim for (twice that is up to 16 % slower, half of it 13-74 %), splits shorter than 4 chunks lose to
+  // their merge (T = 8192 B = 1: 32 splits of 2 chunks 20.5 against 16 of 4 18.4), and from 256 pairs no count wins.
+  // A pinned q8_waves alone keeps the unsplit launch (that knob A/Bs the two wave forms). A pinned count is cut so that
+  // no split is emptier than one chunk at t_cap.
+  if (p.waves == 8 && B > 0 && k.q8_splits != 1 && (k.q8_splits > 1 || k.q8_waves == 0)) {
+    const int ch = 32 * p.kpg;
+    int ns, most;
+    if (k.q8_splits > 1) {
+      ns = k.q8_splits < ATTN_Q8_MAX_SPLITS ? k.q8_splits : ATTN_Q8_MAX_SPLITS;
+      most = (t_cap + ch - 1) / ch;
+    } else {
+      ns = (ATTN_Q8_SPLIT_WGS + pairs - 1) / pairs;
+      most = t_cap / (ATTN_Q8_SPLIT_MIN_CHUNKS * ch);
+    }
+    p.nsplit = ns > most ? (most < 1 ? 1 : most) : ns;
+  }
+  if (p.nsplit > 1) {
+    p.ws_floats = (size_t)B * H * p.nsplit * (ATTN_DH + 4);
+    p.tickets = pairs;
+  }
   return {0, "", p};
 }
 

@@ -168,27 +168,48 @@ int kv8_dequant(const uint8_t* kq, const float* ks, const uint8_t* vq, const flo
 // pairs alone fill the chip). A lane loads 8 bytes of K and 8 of V per key (16 lanes = one 128-B row) and the key's
 // two scales, converts K to packed bf16 in registers (exact) for v_dot2, and V to fp32. The K scale multiplies the
 // score after the dot, score = (q . k_q) * sk / sqrt(Dh); the V scale multiplies p before the accumulation. kv_start,
-// the key mask, t_cap and "rows with no valid key give 0" are v3's. No key splits, no workspace, no packed copy.
-template <int REP, int KPG, int WAVES>
+// the key mask, t_cap and "rows with no valid key give 0" are v3's. No packed copy.
+//
+// SPLIT (8 waves only; few pairs with a long context, where one workgroup per pair leaves most CUs idle): the grid is
+// (nsplit, Hkv, B) and a workgroup streams the keys attn_q8_split_range() (attn_plan.h) gives its split of the pair's
+// valid keys -- the valid range is device state, so the splits cut it, not the cache. Splits without keys exit at once;
+// a pair with one active split (early in a generation) writes its output directly. Otherwise attn_decode_v5_kernel's
+// protocol (attn_decode.hip): a split publishes its unnormalised (m, l, o[128]) per query head (m in log2 units) with
+// write-through (sc1) 16-B stores, every storing wave drains them, one relaxed agent-scope ticket add per workgroup;
+// the workgroup that draws n_act - 1 resets the ticket and merges the splits in split order with sc1 loads. No float
+// atomics, nothing waits, the same bits on every call.
+template <int REP, int KPG, int WAVES, bool SPLIT>
 __global__ void __launch_bounds__(WAVES * 64)
     attn_decode_q8_kernel(const bf16_t* __restrict__ q, const uint8_t* __restrict__ kq, const float* __restrict__ ks,
                           const uint8_t* __restrict__ vq, const float* __restrict__ vs,
                           const int32_t* __restrict__ slot_ptr, const int32_t* __restrict__ kv_start,
-                          const uint8_t* __restrict__ key_mask, int mask_len, bf16_t* __restrict__ out, int H, int Hkv,
-                          int T, int t_cap, float scale) {
+                          const uint8_t* __restrict__ key_mask, int mask_len, bf16_t* __restrict__ out,
+                          float* __restrict__ ws, int32_t* __restrict__ tickets, int nsplit, int H, int Hkv, int T,
+                          int t_cap, float scale) {
+  static_assert(!SPLIT || WAVES == 8, "key splits: the 8-wave form only");
   constexpr int CH = WAVES * 4 * KPG;  // keys per chunk
   constexpr int MW = WAVES > 1 ? WAVES : 1;
   __shared__ float sm_m[WAVES > 1 ? MW : 1][REP];
-  __shared__ float sm_l[WAVES > 1 ? MW : 1][REP];
+  __shared__ float sm_l[WAVES > 1 ? MW : 1][REP];  // (SPLIT: sm_l[0][0] also carries "this workgroup merges")
   __shared__ float sm_o[WAVES > 1 ? MW : 1][WAVES > 1 ? REP : 1][WAVES > 1 ? KV8_DH : 1];
 
-  const int kvh = blockIdx.x, b = blockIdx.y;
+  const int split = SPLIT ? blockIdx.x : 0;
+  const int kvh = SPLIT ? blockIdx.y : blockIdx.x, b = SPLIT ? blockIdx.z : blockIdx.y;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int g = lane >> 4, li = lane & 15;
   const int slot = slot_ptr[0];
   if (slot >= T && threadIdx.x == 0) JLA_FLAG(JLA_BOUNDS_ATTN_T);  // keys past the cache are never read
   const int lo = max(kv_start[b], 0);
-  const int hi_key = min(min(slot + 1, t_cap), T);  // keys [lo, hi_key)
+  int hi_key = min(min(slot + 1, t_cap), T);  // keys [lo, hi_key): the pair's valid keys, or this split's share
+  int c_begin = lo - (lo % CH);
+  int n_act = 1;
+  if constexpr (SPLIT) {
+    const AttnQ8SplitRange sr = attn_q8_split_range(lo, hi_key, CH, nsplit, split);
+    n_act = sr.n_act;
+    // a row with no valid key (n_act 0): split 0 alone goes on, streams nothing and writes 0
+    if (split >= max(n_act, 1)) return;
+    if (n_act > 0) c_begin = sr.c_begin, hi_key = sr.key_end;
+  }
   const int h0 = kvh * REP;
   const uint8_t* mrow = key_mask ? key_mask + (size_t)b * mask_len : nullptr;
   const size_t pair_row = ((size_t)b * Hkv + kvh) * T;
@@ -213,7 +234,6 @@ __global__ void __launch_bounds__(WAVES * 64)
   // base-2 softmax: 1 / sqrt(Dh) and log2 e in one factor, v_exp_f32 directly
   const float scale2 = scale * 1.4426950408889634f;
 
-  const int c_begin = lo - (lo % CH);
   u32x2 kr[KPG], vr[KPG];
   float skr[KPG], svr[KPG];
   auto load = [&](int c0) {
@@ -328,6 +348,81 @@ __global__ void __launch_bounds__(WAVES * 64)
       }
     }
     __syncthreads();
+    if constexpr (SPLIT) {
+      if (n_act > 1) {  // (workgroup-uniform; n_act <= 1 writes the output below, with no workspace traffic)
+        constexpr int HS = KV8_DH + 4;  // floats per head of a partial: [m, l, 0, 0, o[128]]
+        constexpr int PS = REP * HS;    // floats per split partial
+        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+            ws + ((size_t)b * Hkv + kvh) * nsplit * PS, 0, nsplit * PS * 4, 0x00020000);
+        // ---- this split's unnormalised (m, l, o) per head: thread -> (head, 4 dims)
+        for (int it = threadIdx.x; it < REP * 32; it += WAVES * 64) {
+          const int h = it >> 5, d = 4 * (it & 31);
+          float M = -INFINITY;
+#pragma unroll
+          for (int ww = 0; ww < WAVES; ++ww) M = fmaxf(M, sm_m[ww][h]);
+          float num[4] = {0.f, 0.f, 0.f, 0.f}, den = 0.f;
+          if (M != -INFINITY) {
+#pragma unroll
+            for (int ww = 0; ww < WAVES; ++ww) {
+              const float f = __builtin_amdgcn_exp2f(sm_m[ww][h] - M);
+              den += f * sm_l[ww][h];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) num[e] += f * sm_o[ww][h][d + e];
+            }
+          }
+          const int off = (split * PS + h * HS) * 4;
+          __builtin_amdgcn_raw_buffer_store_b128(
+              u32x4{__float_as_uint(num[0]), __float_as_uint(num[1]), __float_as_uint(num[2]), __float_as_uint(num[3])},
+              rs, off + (4 + d) * 4, 0, 16);
+          if (d == 0)
+            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(M), __float_as_uint(den), 0u, 0u}, rs, off, 0,
+                                                   16);
+        }
+        // ---- publish: every storing wave drains its write-through stores, then one ticket add per workgroup
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+          int32_t* tk = tickets + (size_t)b * Hkv + kvh;
+          const int prev = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const bool last = prev == n_act - 1;
+          if (last) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // reset for the next call
+          sm_l[0][0] = last ? 1.f : 0.f;  // (every read of the wave partials is behind the barrier above)
+        }
+        __syncthreads();
+        if (sm_l[0][0] == 0.f) return;
+        // ---- last arriver: online merge of the active splits in split order (sc1 loads, 4 splits in flight; past the
+        // end the last split is re-read, never folded)
+        for (int it = threadIdx.x; it < REP * 32; it += WAVES * 64) {
+          const int h = it >> 5, d = 4 * (it & 31);
+          float Mr = -INFINITY, Lr = 0.f, Or[4] = {0.f, 0.f, 0.f, 0.f};
+          for (int s = 0; s < n_act; s += 4) {
+            u32x4 ml[4], ov[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const int off = (min(s + u, n_act - 1) * PS + h * HS) * 4;
+              ml[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16);
+              ov[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + (4 + d) * 4, 0, 16);
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+              const float ms = __uint_as_float(ml[u][0]);
+              if (s + u >= n_act || ms == -INFINITY) continue;  // (a split whose keys are all masked)
+              const float mn = fmaxf(Mr, ms);
+              const float a = __builtin_amdgcn_exp2f(Mr - mn), f = __builtin_amdgcn_exp2f(ms - mn);  // Mr -inf: a = 0
+              Lr = Lr * a + f * __uint_as_float(ml[u][1]);
+#pragma unroll
+              for (int e = 0; e < 4; ++e) Or[e] = Or[e] * a + f * __uint_as_float(ov[u][e]);
+              Mr = mn;
+            }
+          }
+          u32x2 pk;
+          pk[0] = pack2bf(Lr > 0.f ? Or[0] / Lr : 0.f, Lr > 0.f ? Or[1] / Lr : 0.f);
+          pk[1] = pack2bf(Lr > 0.f ? Or[2] / Lr : 0.f, Lr > 0.f ? Or[3] / Lr : 0.f);
+          *reinterpret_cast<u32x2*>(out + ((size_t)b * H + h0 + h) * KV8_DH + d) = pk;
+        }
+        return;
+      }
+    }
     for (int i = threadIdx.x; i < REP * KV8_DH; i += WAVES * 64) {
       const int h = i / KV8_DH, d = i - h * KV8_DH;
       float M = -INFINITY;
@@ -348,26 +443,32 @@ __global__ void __launch_bounds__(WAVES * 64)
   }
 }
 
-// Launches what attn_decode_q8_plan() (attn_plan.h) names: one instantiation per (rep, kpg, waves) the plan can give.
+// Launches what attn_decode_q8_plan() (attn_plan.h) names: one instantiation per (rep, kpg, waves, split or not) the plan
+// can give. ws / tickets: needed (and checked against the plan, -2) only where the plan splits the keys.
 int attn_decode_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs,
                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
-                   int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s) {
+                   int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws, size_t ws_floats,
+                   int32_t* tickets, int n_tickets) {
   if (B <= 0) return 0;
   const AttnQ8PlanResult r = attn_decode_q8_plan(attn_knobs(), B, H, Hkv, Dh, t_cap, key_mask != nullptr);
   if (r.rc) return r.rc;
   if (t_cap > T || B > 65535) return -1;
   const AttnQ8Plan& p = r.plan;
+  const bool split = p.nsplit > 1;
+  if (split && Hkv > 65535) return -1;  // (the split grid has the kv heads in y)
+  if (split && (!ws || !tickets || ws_floats < p.ws_floats || n_tickets < p.tickets)) return -2;
   const float scale = 1.f / sqrtf((float)Dh);
-  const dim3 grid(Hkv, B);
-#define JLA_ADQ8(R, K, W)                                                                                           \
-  if (p.rep == R && p.kpg == K && p.waves == W) {                                                                   \
-    attn_decode_q8_kernel<R, K, W><<<grid, W * 64, 0, s>>>(q, kq, ks, vq, vs, slot, kv_start, key_mask, mask_len,    \
-                                                           out, H, Hkv, T, t_cap, scale);                           \
+  const dim3 grid = split ? dim3(p.nsplit, Hkv, B) : dim3(Hkv, B);
+#define JLA_ADQ8(R, K, W, S)                                                                                        \
+  if (p.rep == R && p.kpg == K && p.waves == W && split == S) {                                                     \
+    attn_decode_q8_kernel<R, K, W, S><<<grid, W * 64, 0, s>>>(q, kq, ks, vq, vs, slot, kv_start, key_mask, mask_len, \
+                                                              out, ws, tickets, p.nsplit, H, Hkv, T, t_cap, scale); \
     JLA_CHECK_LAUNCH();                                                                                             \
     return 0;                                                                                                       \
   }
-  JLA_ADQ8(1, 8, 8) JLA_ADQ8(2, 8, 8) JLA_ADQ8(4, 4, 8) JLA_ADQ8(8, 2, 8)
-  JLA_ADQ8(1, 8, 1) JLA_ADQ8(2, 8, 1) JLA_ADQ8(4, 4, 1) JLA_ADQ8(8, 2, 1)
+  JLA_ADQ8(1, 8, 8, false) JLA_ADQ8(2, 8, 8, false) JLA_ADQ8(4, 4, 8, false) JLA_ADQ8(8, 2, 8, false)
+  JLA_ADQ8(1, 8, 1, false) JLA_ADQ8(2, 8, 1, false) JLA_ADQ8(4, 4, 1, false) JLA_ADQ8(8, 2, 1, false)
+  JLA_ADQ8(1, 8, 8, true) JLA_ADQ8(2, 8, 8, true) JLA_ADQ8(4, 4, 8, true) JLA_ADQ8(8, 2, 8, true)
 #undef JLA_ADQ8
   return -1;
 }

@@ -142,6 +142,7 @@ void attn_set_v5_fold(int n);
 void attn_set_v6(int mode);
 void attn_set_v6_wpp(int wpp);
 void attn_set_q8_waves(int waves);  // the fp8 KV cache's kernel: 1 / 8 waves per pair pinned; 0: by shape
+void attn_set_q8_splits(int n);     // ... its key splits per pair: 0 by shape, 1 never, n > 1 pinned (the plan clamps it)
 void attn_set_diag(int d);     // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)
 void attn_set_v6_diag(int d);  // tools only: v6 ablations (1 no compute, 2 no K loads, 4 no V DMAs; wrong results)
 // bounds-checked debug build: per-translation-unit error words (JLA_BOUNDS_* bits; 0 in release builds)
@@ -174,10 +175,12 @@ int rope_kv_write_q8(const bf16_t* qkv, const float* table, int table_len, const
 int kv8_dequant(const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs, bf16_t* kout, bf16_t* vout,
                 int pairs, int T, int n, int n_out, hipStream_t s);
 // decode attention on the fp8 bytes, launched as attn_decode_q8_plan() (attn_plan.h) says; returns the plan's rc where
-// it refuses
+// it refuses. Where the plan splits the keys (nsplit > 1) ws / tickets hold the plan's ws_floats / tickets (tickets
+// zero-initialised once, self-resetting), -2 if they do not; an unsplit launch ignores them.
 int attn_decode_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs,
                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
-                   int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s);
+                   int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws = nullptr,
+                   size_t ws_floats = 0, int32_t* tickets = nullptr, int n_tickets = 0);
 void attn_prefill_set_impl(int impl);  // 2 = GQA-shared MFMA 32x32 flash kernel (default), 1 = v1
 int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                  const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,

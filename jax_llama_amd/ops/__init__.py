@@ -697,8 +697,16 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
         if out_packed is not None:
             raise ValueError("attention: no packed output copy with an Fp8KV cache (attention_packs)")
         if s == 1:  # straight on the fp8 bytes (csrc/kernels/kv8.hip attn_decode_q8)
+            # one plan call (csrc/kernels/attn_plan.h): few pairs with a long context split the keys, and that launch
+            # needs the partials' workspace and one ticket per pair; a shape the plan refuses is reported by the launch
+            _rc, _why, nsplit, ws_floats, n_tickets = e.attn_decode_q8_split_check(
+                bsz, h, k_cache.shape[1], dh, t_cap, key_mask is not None)
+            ws = tickets = None
+            if nsplit > 1:
+                ws = workspace.get("attn_q8", ws_floats, torch.float32, q.device)
+                tickets = workspace.get_zeroed("attn_q8_tickets", n_tickets, torch.int32, q.device)
             e.attn_decode_q8(q, k_cache.q, k_cache.scale, v_cache.q, v_cache.scale, slot_t, kv_start, key_mask, out,
-                             t_cap)
+                             t_cap, ws, tickets)
         else:
             # the rows the queries can see, dequantised (exact) into a scratch exactly that long: attn_prefill clamps
             # the key rows it loads to its cache length, so it reads no scratch row that kv8_dequant did not write.

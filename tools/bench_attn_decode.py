@@ -14,7 +14,9 @@ impl (ext.attn_set_impl / attn_set_v3_max_pairs): 2 = default dispatch; 3 = v3 (
 
 --kv fp8: the FP8 (e4m3) KV cache's kernel (csrc/kernels/kv8.hip) on a cache of random codes, beside the bf16 kernels on
 the bf16 cache that holds the same (dequantised) values, alternating in one process; --q8-waves pins its waves per pair
-(0: the plan's choice). Every record carries the median and the minimum over the rounds and GB/s (the valid K / V bytes
+(0: the plan's choice) and --q8-splits its key splits per pair (0: the plan's choice, 1: never split, n: pinned; the
+plan's resulting count goes into the record as q8_splits, the pinned value as q8_splits_pin); every (waves, splits)
+combination is one run. Every record carries the median and the minimum over the rounds and GB/s (the valid K / V bytes
 of the format, scales included, over the median).
 """
 from __future__ import annotations
@@ -61,6 +63,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"])
     ap.add_argument("--q8-waves", type=int, nargs="+", default=[0], help="fp8: waves per pair pinned (0: by shape)")
+    ap.add_argument("--q8-splits", type=int, nargs="+", default=[0],
+                    help="fp8: key splits per pair pinned (0: by shape, 1: never)")
     args = ap.parse_args()
     e = ops.ext()
     cfg = get_preset(args.model)
@@ -90,14 +94,27 @@ def main():
         ks = torch.zeros(b, dtype=torch.int32, device="cuda")
         res, first = {}, None
         graphs = {}
-        runs = [("bf16", i) for i in args.impls if "bf16" in args.kv] + [("fp8", w) for w in args.q8_waves if k8]
+        runs = [("bf16", i) for i in args.impls if "bf16" in args.kv]
+        runs += [("fp8", w, n) for w in args.q8_waves for n in args.q8_splits if k8]
+
+        def pin(run):
+            set_impl(e, run[1] if run[0] == "bf16" else 2)
+            if run[0] == "fp8":
+                e.attn_set_q8_waves(run[1])
+                e.attn_set_q8_splits(run[2])
+            return (kc, vc) if run[0] == "bf16" else (k8, v8)
+
+        # every run once before the first capture: the workspaces (grow-only) reach the size of the largest run, so no
+        # later run reallocates a buffer whose address an earlier run's graph has recorded
         for run in runs:
-            kv, impl = run
-            set_impl(e, impl if kv == "bf16" else 2)
-            if kv == "fp8":
-                e.attn_set_q8_waves(impl)
-            ck, cv = (kc, vc) if kv == "bf16" else (k8, v8)
-            out = ops.attention(q, ck, cv, slot, ks)  # sizes the workspaces before capture
+            ck, cv = pin(run)
+            ops.attention(q, ck, cv, slot, ks)
+        torch.cuda.synchronize()
+        ws_generation = ops.workspace.generation
+        for run in runs:
+            kv, impl = run[:2]
+            ck, cv = pin(run)
+            out = ops.attention(q, ck, cv, slot, ks)
             torch.cuda.synchronize()
             first = out.float() if first is None else first
             diff = float((out.float() - first).abs().max())
@@ -110,14 +127,16 @@ def main():
                 for _ in range(args.reps):
                     flush.fill_(1)
             waves = e.attn_decode_q8_plan_check(b, h, hkv, hd, tc, False)[2] if kv == "fp8" else None
-            graphs[run] = (ga, gf, diff, waves)
+            nsplit = e.attn_decode_q8_split_check(b, h, hkv, hd, tc, False)[2] if kv == "fp8" else None
+            graphs[run] = (ga, gf, diff, waves, nsplit)
         e.attn_set_v6_diag(0)
         e.attn_reset_knobs()
+        assert ops.workspace.generation == ws_generation, "a workspace moved after a graph recorded its address"
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         times = {run: [] for run in runs}
         for _ in range(args.rounds):
             for run in runs:
-                ga, gf, _, _ = graphs[run]
+                ga, gf = graphs[run][:2]
                 tt = []
                 for gr in (ga, gf):
                     gr.replay()
@@ -128,13 +147,15 @@ def main():
                     tt.append(ev0.elapsed_time(ev1))
                 times[run].append((tt[0] - tt[1]) * 1000.0 / args.reps)
         for run in runs:
-            kv, impl = run
+            kv, impl = run[:2]
             ts = sorted(times[run])
             med = ts[len(ts) // 2]
             nbytes = b * hkv * t * 2 * (hd + 4 if kv == "fp8" else 2 * hd)  # the valid K and V rows of the format
             res = {"op": "attn_decode_graph", "model": args.model, "tp": args.tp, "b": b, "t": t, "cache_len": tc,
                    "kv": kv, "impl": impl if kv == "bf16" else None, "q8_waves": graphs[run][3],
+                   "q8_splits": graphs[run][4], "q8_splits_pin": run[2] if kv == "fp8" else None,
                    "us": round(ts[0], 2), "us_median": round(med, 2), "kv_bytes": nbytes,
+                   "us_max": round(ts[-1], 2),
                    "gbps": round(nbytes / med / 1e3, 1), "max_diff_vs_first": round(graphs[run][2], 5)}
             print(json.dumps(res), flush=True)
         del graphs, kc, vc, k8, v8
