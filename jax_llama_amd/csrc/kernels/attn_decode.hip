@@ -10,9 +10,10 @@
 // attn_decode_plan() (attn_plan.h), and attn_decode() at the end of this file launches what the plan names.
 // With splits, each split publishes (m, l, o[Dh]) with write-through stores and bumps a per-pair ticket; the last
 // arriver merges the splits (log-sum-exp), so decode attention is ONE launch (cdna_hip_programming.md Guideline 16,
-// sc1-store / sc1-load form; the last arriver resets the ticket for the next replay).
+// sc1-store / sc1-load form; the last arriver resets the ticket for the next replay): attn_merge.h has the protocol
+// and v3's / v5's share of it, v2 keeps its own form (one wave per split).
 // Rows with no valid key produce 0 (never NaN: -inf maxima are guarded).
-#include "attn_plan.h"
+#include "attn_merge.h"
 #include "common.h"
 #include "launchers.h"
 
@@ -139,45 +140,17 @@ __global__ void __launch_bounds__(AD3_WAVES * 64)
       }
     }
   }
-  // ---- per wave: sum the 4 groups (same max), then merge the 8 waves through LDS
+  // ---- per wave: sum the 4 groups (same max), then merge the 8 waves through LDS (attn_merge.h)
 #pragma unroll
   for (int h = 0; h < REP; ++h) {
-    float l = l_h[h];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float v = o[h][e];
-      v += __shfl_xor(v, 16, 64);
-      v += __shfl_xor(v, 32, 64);
-      o[h][e] = v;
-    }
-    if (g == 0) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sm_o[w][h][8 * li + e] = o[h][e];
-      if (li == 0) {
-        sm_m[w][h] = m_h[h];
-        sm_l[w][h] = l;  // sum over the 4 groups (lanes li, li + 16, li + 32, li + 48)
-      }
-    }
+    wave_sum_groups(l_h[h], o[h], o[h]);
+    wave_put(sm_m, sm_l, sm_o, w, h, g, li, m_h[h], l_h[h], o[h]);
   }
   __syncthreads();
   for (int i = threadIdx.x; i < REP * AD_DH; i += AD3_WAVES * 64) {
     const int h = i / AD_DH, d = i - h * AD_DH;
-    float M = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < AD3_WAVES; ++ww) M = fmaxf(M, sm_m[ww][h]);
-    float num = 0.f, den = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int ww = 0; ww < AD3_WAVES; ++ww) {
-        const float mw = sm_m[ww][h];
-        const float f = mw == -INFINITY ? 0.f : __expf(mw - M);
-        num += f * sm_o[ww][h][d];
-        den += f * sm_l[ww][h];
-      }
-    }
-    const bf16_t r = f2bf(den > 0.f ? num / den : 0.f);
+    const Merged1 c = waves_combine1<ExpNat>(sm_m, sm_l, sm_o, h, d);
+    const bf16_t r = f2bf(c.den > 0.f ? c.num / c.den : 0.f);
     out[((size_t)b * H + h0 + h) * AD_DH + d] = r;
     if (out_pack) out_pack[pack_off(b, (h0 + h) * AD_DH + d, H * AD_DH)] = r;  // the o projection's packed x
   }
@@ -188,11 +161,10 @@ __global__ void __launch_bounds__(AD3_WAVES * 64)
 // pair's scoring is compute-bound on one CU (Llama-3-70B at MP 8, B = 1: 8 q heads x ~200 keys on a single CU,
 // 13 us per layer in the decode trace). Here the valid keys [kv_start, slot] are cut into CH-key splits, one
 // 4-wave workgroup each (every K / V row of the split issued at once: one memory round trip), scores by v_dot2,
-// a per-wave online softmax, one LDS merge of the 4 waves; a split publishes its (m, l, o) with write-through (sc1)
-// 16-B stores and takes the pair's agent-scope ticket, and the last arriver merges the splits in split order
-// (sc1 loads; cdna_hip_programming.md Guideline 16 R1 form) and writes the output (+ the packed copy for the o
-// projection). Splits outside the valid key range exit at once (the grid covers the whole cache, the valid range is
-// device state), so the ticket counts only the active splits; a pair with one active split writes directly.
+// a per-wave online softmax, one LDS merge of the 4 waves; the splits of a pair publish, arrive and merge by the
+// key-split protocol of attn_merge.h, and the last arriver writes the output (+ the packed copy for the o projection).
+// The grid covers the whole cache and the valid range is device state: splits outside it exit at once, so the ticket
+// counts only the active splits [s_lo, s_hi); a pair with one active split writes directly.
 constexpr int AD5_WAVES = 4;
 // AD5_FOLD: splits the last arriver merges per round (all of a round's partial loads in flight together), 4 or 12
 
@@ -203,9 +175,7 @@ __global__ void __launch_bounds__(AD5_WAVES * 64)
                           const uint8_t* __restrict__ key_mask, int mask_len, bf16_t* __restrict__ out,
                           float* __restrict__ ws, int32_t* __restrict__ tickets, int H, int Hkv, int T, int t_cap,
                           int nsplit, float scale, bf16_t* __restrict__ out_pack) {
-  constexpr int CH = AD5_WAVES * 4 * KPG;     // keys per split
-  constexpr int HS = AD_DH + 4;               // floats per head of a partial: [m, l, 0, 0, o[128]]
-  constexpr int PS = REP * HS;                // floats per split partial
+  constexpr int CH = AD5_WAVES * 4 * KPG;  // keys per split
   __shared__ float sm_m[AD5_WAVES][REP];
   __shared__ float sm_l[AD5_WAVES][REP];
   __shared__ float sm_o[AD5_WAVES][REP][AD_DH];
@@ -291,103 +261,36 @@ __global__ void __launch_bounds__(AD5_WAVES * 64)
         for (int e = 0; e < 8; ++e) o[e] += p * vf[e];
       }
     }
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      o[e] += __shfl_xor(o[e], 16, 64);
-      o[e] += __shfl_xor(o[e], 32, 64);
-    }
-    if (g == 0) {
-#pragma unroll
-      for (int e = 0; e < 8; ++e) sm_o[w][h][8 * li + e] = o[e];
-      if (li == 0) {
-        sm_m[w][h] = mx;
-        sm_l[w][h] = l;
-      }
-    }
+    wave_sum_groups(l, o, o);
+    wave_put(sm_m, sm_l, sm_o, w, h, g, li, mx, l, o);
   }
   __syncthreads();
 
-  // ---- the workgroup's (m, l, o) per head: thread -> (head, 4 dims)
-  const __amdgpu_buffer_rsrc_t rs =
-      __builtin_amdgcn_make_buffer_rsrc(ws + ((size_t)b * Hkv + kvh) * nsplit * PS, 0, nsplit * PS * 4, 0x00020000);
+  // ---- the workgroup's (m, l, o) per head, thread -> (head, 4 dims): the output, or this split's partial
+  const size_t pair = (size_t)b * Hkv + kvh;
+  const __amdgpu_buffer_rsrc_t rs = split_parts_rsrc<REP>(ws, pair, nsplit);
   for (int it = threadIdx.x; it < REP * 32; it += AD5_WAVES * 64) {
     const int h = it >> 5, d = 4 * (it & 31);
-    float M = -INFINITY;
-#pragma unroll
-    for (int ww = 0; ww < AD5_WAVES; ++ww) M = fmaxf(M, sm_m[ww][h]);
-    float num[4] = {0.f, 0.f, 0.f, 0.f}, den = 0.f;
-    if (M != -INFINITY) {
-#pragma unroll
-      for (int ww = 0; ww < AD5_WAVES; ++ww) {
-        const float mw = sm_m[ww][h];
-        const float f = mw == -INFINITY ? 0.f : __expf(mw - M);
-        den += f * sm_l[ww][h];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) num[e] += f * sm_o[ww][h][d + e];
-      }
-    }
+    const Merged4 c = waves_combine4<ExpNat>(sm_m, sm_l, sm_o, h, d);
     if (n_act == 1) {
       float v[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) v[e] = den > 0.f ? num[e] / den : 0.f;
+      for (int e = 0; e < 4; ++e) v[e] = c.den > 0.f ? c.num[e] / c.den : 0.f;
       store_out(h, d, v);
     } else {
-      const int off = (split * PS + h * HS) * 4;
-      __builtin_amdgcn_raw_buffer_store_b128(
-          u32x4{__float_as_uint(num[0]), __float_as_uint(num[1]), __float_as_uint(num[2]), __float_as_uint(num[3])},
-          rs, off + (4 + d) * 4, 0, 16);
-      if (d == 0)
-        __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(M), __float_as_uint(den), 0u, 0u}, rs, off, 0, 16);
+      split_part_store<REP>(rs, split, h, d, c);
     }
   }
   if (n_act == 1) return;
+  if (!split_arrive(tickets, pair, n_act, last_flag)) return;
 
-  // ---- publish: every storing wave drains its write-through stores, then one ticket add per workgroup
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int32_t* tk = tickets + (size_t)b * Hkv + kvh;
-    const int prev = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == n_act - 1;
-    if (last) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // reset for the next call
-    last_flag = last;
-  }
-  __syncthreads();
-  if (!last_flag) return;
-
-  // ---- last arriver: online merge of the active splits in split order (sc1 loads, 4 splits in flight)
+  // ---- last arriver: the active splits in split order, AD5_FOLD per load round (T = 384 at rep 8 is 12 splits)
   for (int it = threadIdx.x; it < REP * 32; it += AD5_WAVES * 64) {
     const int h = it >> 5, d = 4 * (it & 31);
-    float Mr = -INFINITY, Lr = 0.f, Or[4] = {0.f, 0.f, 0.f, 0.f};
-    auto fold = [&](const u32x4 ml, const u32x4 ov) {
-      const float ms = __uint_as_float(ml[0]);
-      if (ms == -INFINITY) return;
-      const float mn = fmaxf(Mr, ms);
-      const float a = Mr == -INFINITY ? 0.f : __expf(Mr - mn), f = __expf(ms - mn);
-      Lr = Lr * a + f * __uint_as_float(ml[1]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) Or[e] = Or[e] * a + f * __uint_as_float(ov[e]);
-      Mr = mn;
-    };
-    // AD5_FOLD splits per round, all loads of a round in flight together (one dependent L2 round trip per round,
-    // not one per 4 splits: T = 384 at rep 8 is 12 splits); past the end the last split is re-read, never folded
-    for (int s = s_lo; s < s_hi; s += AD5_FOLD) {
-      u32x4 ml[AD5_FOLD], ov[AD5_FOLD];
-#pragma unroll
-      for (int u = 0; u < AD5_FOLD; ++u) {
-        const int off = (min(s + u, s_hi - 1) * PS + h * HS) * 4;
-        ml[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16);
-        ov[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + (4 + d) * 4, 0, 16);
-      }
-#pragma unroll
-      for (int u = 0; u < AD5_FOLD; ++u)
-        if (s + u < s_hi) fold(ml[u], ov[u]);
-    }
+    const Merged4 c = split_merge<ExpNat, AD5_FOLD, REP>(rs, s_lo, s_hi, h, d);
     float v[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) v[e] = Lr > 0.f ? Or[e] / Lr : 0.f;
+    for (int e = 0; e < 4; ++e) v[e] = c.den > 0.f ? c.num[e] / c.den : 0.f;
     store_out(h, d, v);
   }
 }

@@ -11,6 +11,7 @@
 namespace jla {
 
 constexpr int ATTN_DH = 128;               // the only head dim the kernels are built for
+constexpr int ATTN_PART_FLOATS = ATTN_DH + 4;  // a key split's partial per head, [m, l, 0, 0, o[128]] (attn_merge.h)
 constexpr int ATTN_V2_MIN_PAIRS = 4096;    // v2 / v4 stream whole (row, kv head) pairs from here (B = 512 at 8 kv heads)
 constexpr int ATTN_MASK_PACK_MAX_B = 32;   // with a key mask, no packed copy above this many rows (the last rule below)
 
@@ -155,7 +156,7 @@ inline AttnPlanResult attn_decode_plan(const AttnKnobs& k, int B, int H, int Hkv
   // nothing), and one ticket per pair. It is what the callers always allocated: sizing each kernel exactly (nothing for
   // v4 at the headline shape) moves every later allocation, and measured 0.3 % slower on the headline in two sessions
   // (profiles/attn_plan_resolver_headline.jsonl).
-  p.ws_floats = (size_t)B * H * p.nsplit * (ATTN_DH + 4);
+  p.ws_floats = (size_t)B * H * p.nsplit * ATTN_PART_FLOATS;
   p.tickets = pairs;
   return {0, "", p};
 }
@@ -271,7 +272,7 @@ inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, in
     p.nsplit = ns > most ? (most < 1 ? 1 : most) : ns;
   }
   if (p.nsplit > 1) {
-    p.ws_floats = (size_t)B * H * p.nsplit * (ATTN_DH + 4);
+    p.ws_floats = (size_t)B * H * p.nsplit * ATTN_PART_FLOATS;
     p.tickets = pairs;
   }
   return {0, "", p};

@@ -7,7 +7,7 @@
 // [-100, 100], 0 for an all-zero row; q = fp8_rne(row / 2^e). q * 2^e is exact in bf16, and the model with this cache
 // is the bf16 model whose K / V rows are replaced by q * 2^e when they are written. 132 bytes per row instead of 256.
 // gfx950's FP8 conversions are OCP (e4m3fn), not fnuz.
-#include "attn_plan.h"
+#include "attn_merge.h"
 #include "common.h"
 #include "launchers.h"
 
@@ -173,11 +173,9 @@ int kv8_dequant(const uint8_t* kq, const float* ks, const uint8_t* vq, const flo
 // SPLIT (8 waves only; few pairs with a long context, where one workgroup per pair leaves most CUs idle): the grid is
 // (nsplit, Hkv, B) and a workgroup streams the keys attn_q8_split_range() (attn_plan.h) gives its split of the pair's
 // valid keys -- the valid range is device state, so the splits cut it, not the cache. Splits without keys exit at once;
-// a pair with one active split (early in a generation) writes its output directly. Otherwise attn_decode_v5_kernel's
-// protocol (attn_decode.hip): a split publishes its unnormalised (m, l, o[128]) per query head (m in log2 units) with
-// write-through (sc1) 16-B stores, every storing wave drains them, one relaxed agent-scope ticket add per workgroup;
-// the workgroup that draws n_act - 1 resets the ticket and merges the splits in split order with sc1 loads. No float
-// atomics, nothing waits, the same bits on every call.
+// a pair with one active split (early in a generation) writes its output directly. Otherwise the key-split protocol of
+// attn_merge.h over the active splits [0, n_act), m in log2 units: no float atomics, nothing waits, the same bits on
+// every call.
 template <int REP, int KPG, int WAVES, bool SPLIT>
 __global__ void __launch_bounds__(WAVES * 64)
     attn_decode_q8_kernel(const bf16_t* __restrict__ q, const uint8_t* __restrict__ kq, const float* __restrict__ ks,
@@ -310,19 +308,7 @@ __global__ void __launch_bounds__(WAVES * 64)
   // ---- per wave: sum the 4 groups (same max)
   float of[REP][8];
 #pragma unroll
-  for (int h = 0; h < REP; ++h) {
-    float l = l_h[h];
-    l += __shfl_xor(l, 16, 64);
-    l += __shfl_xor(l, 32, 64);
-    l_h[h] = l;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-      float v = o[h][e >> 1][e & 1];
-      v += __shfl_xor(v, 16, 64);
-      v += __shfl_xor(v, 32, 64);
-      of[h][e] = v;
-    }
-  }
+  for (int h = 0; h < REP; ++h) wave_sum_groups(l_h[h], o[h], of[h]);
   if constexpr (WAVES == 1) {
     if (g == 0) {
 #pragma unroll
@@ -337,87 +323,27 @@ __global__ void __launch_bounds__(WAVES * 64)
   } else {
     // ---- merge the waves through LDS
 #pragma unroll
-    for (int h = 0; h < REP; ++h) {
-      if (g == 0) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) sm_o[w][h][8 * li + e] = of[h][e];
-        if (li == 0) {
-          sm_m[w][h] = m_h[h];
-          sm_l[w][h] = l_h[h];
-        }
-      }
-    }
+    for (int h = 0; h < REP; ++h) wave_put(sm_m, sm_l, sm_o, w, h, g, li, m_h[h], l_h[h], of[h]);
     __syncthreads();
     if constexpr (SPLIT) {
       if (n_act > 1) {  // (workgroup-uniform; n_act <= 1 writes the output below, with no workspace traffic)
-        constexpr int HS = KV8_DH + 4;  // floats per head of a partial: [m, l, 0, 0, o[128]]
-        constexpr int PS = REP * HS;    // floats per split partial
-        const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-            ws + ((size_t)b * Hkv + kvh) * nsplit * PS, 0, nsplit * PS * 4, 0x00020000);
+        const size_t pair = (size_t)b * Hkv + kvh;
+        const __amdgpu_buffer_rsrc_t rs = split_parts_rsrc<REP>(ws, pair, nsplit);
         // ---- this split's unnormalised (m, l, o) per head: thread -> (head, 4 dims)
         for (int it = threadIdx.x; it < REP * 32; it += WAVES * 64) {
           const int h = it >> 5, d = 4 * (it & 31);
-          float M = -INFINITY;
-#pragma unroll
-          for (int ww = 0; ww < WAVES; ++ww) M = fmaxf(M, sm_m[ww][h]);
-          float num[4] = {0.f, 0.f, 0.f, 0.f}, den = 0.f;
-          if (M != -INFINITY) {
-#pragma unroll
-            for (int ww = 0; ww < WAVES; ++ww) {
-              const float f = __builtin_amdgcn_exp2f(sm_m[ww][h] - M);
-              den += f * sm_l[ww][h];
-#pragma unroll
-              for (int e = 0; e < 4; ++e) num[e] += f * sm_o[ww][h][d + e];
-            }
-          }
-          const int off = (split * PS + h * HS) * 4;
-          __builtin_amdgcn_raw_buffer_store_b128(
-              u32x4{__float_as_uint(num[0]), __float_as_uint(num[1]), __float_as_uint(num[2]), __float_as_uint(num[3])},
-              rs, off + (4 + d) * 4, 0, 16);
-          if (d == 0)
-            __builtin_amdgcn_raw_buffer_store_b128(u32x4{__float_as_uint(M), __float_as_uint(den), 0u, 0u}, rs, off, 0,
-                                                   16);
+          split_part_store<REP>(rs, split, h, d, waves_combine4<ExpLog2>(sm_m, sm_l, sm_o, h, d));
         }
-        // ---- publish: every storing wave drains its write-through stores, then one ticket add per workgroup
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (threadIdx.x == 0) {
-          int32_t* tk = tickets + (size_t)b * Hkv + kvh;
-          const int prev = __hip_atomic_fetch_add(tk, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          const bool last = prev == n_act - 1;
-          if (last) __hip_atomic_store(tk, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // reset for the next call
-          sm_l[0][0] = last ? 1.f : 0.f;  // (every read of the wave partials is behind the barrier above)
-        }
-        __syncthreads();
-        if (sm_l[0][0] == 0.f) return;
-        // ---- last arriver: online merge of the active splits in split order (sc1 loads, 4 splits in flight; past the
-        // end the last split is re-read, never folded)
+        // (the flag in sm_l[0][0]: every read of the wave partials is behind the barrier inside)
+        if (!split_arrive(tickets, pair, n_act, sm_l[0][0])) return;
+        // ---- last arriver: the active splits [0, n_act) in split order, 4 per load round
         for (int it = threadIdx.x; it < REP * 32; it += WAVES * 64) {
           const int h = it >> 5, d = 4 * (it & 31);
-          float Mr = -INFINITY, Lr = 0.f, Or[4] = {0.f, 0.f, 0.f, 0.f};
-          for (int s = 0; s < n_act; s += 4) {
-            u32x4 ml[4], ov[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const int off = (min(s + u, n_act - 1) * PS + h * HS) * 4;
-              ml[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16);
-              ov[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, off + (4 + d) * 4, 0, 16);
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-              const float ms = __uint_as_float(ml[u][0]);
-              if (s + u >= n_act || ms == -INFINITY) continue;  // (a split whose keys are all masked)
-              const float mn = fmaxf(Mr, ms);
-              const float a = __builtin_amdgcn_exp2f(Mr - mn), f = __builtin_amdgcn_exp2f(ms - mn);  // Mr -inf: a = 0
-              Lr = Lr * a + f * __uint_as_float(ml[u][1]);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) Or[e] = Or[e] * a + f * __uint_as_float(ov[u][e]);
-              Mr = mn;
-            }
-          }
+          const Merged4 c = split_merge<ExpLog2, 4, REP>(rs, 0, n_act, h, d);
+          const float Lr = c.den;
           u32x2 pk;
-          pk[0] = pack2bf(Lr > 0.f ? Or[0] / Lr : 0.f, Lr > 0.f ? Or[1] / Lr : 0.f);
-          pk[1] = pack2bf(Lr > 0.f ? Or[2] / Lr : 0.f, Lr > 0.f ? Or[3] / Lr : 0.f);
+          pk[0] = pack2bf(Lr > 0.f ? c.num[0] / Lr : 0.f, Lr > 0.f ? c.num[1] / Lr : 0.f);
+          pk[1] = pack2bf(Lr > 0.f ? c.num[2] / Lr : 0.f, Lr > 0.f ? c.num[3] / Lr : 0.f);
           *reinterpret_cast<u32x2*>(out + ((size_t)b * H + h0 + h) * KV8_DH + d) = pk;
         }
         return;
@@ -425,20 +351,8 @@ __global__ void __launch_bounds__(WAVES * 64)
     }
     for (int i = threadIdx.x; i < REP * KV8_DH; i += WAVES * 64) {
       const int h = i / KV8_DH, d = i - h * KV8_DH;
-      float M = -INFINITY;
-#pragma unroll
-      for (int ww = 0; ww < WAVES; ++ww) M = fmaxf(M, sm_m[ww][h]);
-      float num = 0.f, den = 0.f;
-      if (M != -INFINITY) {
-#pragma unroll
-        for (int ww = 0; ww < WAVES; ++ww) {
-          const float mw = sm_m[ww][h];
-          const float f = __builtin_amdgcn_exp2f(mw - M);  // (log2 units; a wave without a key: exp2(-inf) = 0)
-          num += f * sm_o[ww][h][d];
-          den += f * sm_l[ww][h];
-        }
-      }
-      out[((size_t)b * H + h0 + h) * KV8_DH + d] = f2bf(den > 0.f ? num / den : 0.f);
+      const Merged1 c = waves_combine1<ExpLog2>(sm_m, sm_l, sm_o, h, d);
+      out[((size_t)b * H + h0 + h) * KV8_DH + d] = f2bf(c.den > 0.f ? c.num / c.den : 0.f);
     }
   }
 }
