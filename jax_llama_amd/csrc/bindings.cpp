@@ -753,7 +753,7 @@ void logprob_rows(Tensor logits, Tensor targets, int64_t col_offset, Tensor tgt,
      "logprob_rows");
 }
 
-// stage 1 of the sampler: per-4096-chunk top-K candidates (global indices = local + idx_offset)
+// stage 1 of the sampler: per-16384-chunk (jla::topk_chunks) top-K candidates (global indices = local + idx_offset)
 void topk_chunk(Tensor logits, int64_t k, int64_t idx_offset, Tensor cv, Tensor ci) {
   for (auto* t : {&logits, &cv, &ci}) check_gpu(*t, "topk_chunk arg");
   check(logits.scalar_type() == torch::kFloat32 && logits.dim() == 2, "logits must be fp32 [B, V]");

@@ -3,8 +3,8 @@
 // generation.py:28-41 with do_sample = temperature != 0, top_k = 50).
 //
 // Two kernels, no host sync, hipGraph-capturable:
-//   topk_chunk:  grid (ceil(V/4096), B). A 256-thread workgroup holds a 4096-logit chunk in
-//                registers (16 keys per thread, order-preserving uint32 of the fp32 logit) and finds
+//   topk_chunk:  grid (ceil(V/16384), B). A 256-thread workgroup holds a 16384-logit chunk (TK_CHUNK) in
+//                registers (TK_E = 64 keys per thread, order-preserving uint32 of the fp32 logit) and finds
 //                the chunk's K-th largest key by 4-pass LDS radix select (8 bits per pass, one wave
 //                scans the 256-bin histogram with DPP-free shuffles). It emits exactly K candidates:
 //                everything above the threshold plus the lowest-index ties.
@@ -24,8 +24,10 @@ namespace jla {
 
 constexpr int TK_THREADS = 256, TK_E = 64, TK_CHUNK = TK_THREADS * TK_E;
 
+// -0.0 takes the key of +0.0: the two are equal logits (a tie goes to the lower index, like any other), not neighbours
 JLA_DEV uint32_t fkey(float f) {
-  const uint32_t u = __float_as_uint(f);
+  uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 JLA_DEV float kfloat(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }

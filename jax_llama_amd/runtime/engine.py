@@ -149,6 +149,7 @@ class DecodeEngine:
         self.cur_len = torch.zeros(1, **i32)
         self.sequences = torch.zeros(batch_size, max_length, **i32)
         self.key_mask: Optional[torch.Tensor] = None
+        self._key_mask_buf: Optional[torch.Tensor] = None  # a holed mask lives here: the graph records its address
         self._graph = None
         self._graph_key = None
         self.keep_graph = False  # keep the captured graph's topology (runtime/benchmark.py counts its kernel nodes)
@@ -204,6 +205,11 @@ class DecodeEngine:
         from ..models.llama import mask_to_kv_start
         kv_start, key_mask = mask_to_kv_start(ext_mask, dev)
         self.kv_start.copy_(kv_start)
+        if key_mask is not None:
+            if self._key_mask_buf is None:
+                self._key_mask_buf = torch.empty_like(key_mask)
+            self._key_mask_buf.copy_(key_mask)
+            key_mask = self._key_mask_buf
         self.key_mask = key_mask
         self.cache.reset()
         self.sequences.fill_(self.gc.pad_token_id)
@@ -252,9 +258,15 @@ class DecodeEngine:
         return self.prefill(input_ids, attention_mask)
 
     def _graph_state(self):
-        # the graph records buffer addresses: the scratch workspaces (ops.workspace) and the sampling mode
-        return (self.gc.do_sample, self.key_mask is not None, ops.workspace.generation, _fused_greedy(),
-                ops.ARGMAX_FUSED_MIN_M, ops.SKINNY_ARGMAX, ops.QKV_ATTN, self.model.comm.reduce_dtype)
+        # the graph records buffer addresses (the scratch workspaces of ops.workspace; the state buffers and a holed key
+        # mask are this engine's own, fixed ones), the sampling mode, and the scalars its launches take by value:
+        # pad and eos (decode_update) and the sampler's settings (topk_merge). A call with other values captures again
+        # (so does every new seed of a sampling caller: the seed is a launch argument, not a device word).
+        gc = self.gc
+        sampler = (gc.top_k, gc.temperature, gc.top_p, int(gc.seed)) if gc.do_sample else None
+        return (gc.do_sample, self.key_mask is not None, ops.workspace.generation, _fused_greedy(),
+                ops.ARGMAX_FUSED_MIN_M, ops.SKINNY_ARGMAX, ops.QKV_ATTN, self.model.comm.reduce_dtype,
+                int(gc.pad_token_id), int(gc.eos_token_id), sampler)
 
     def _ensure_graph(self):
         if self._graph is not None and self._graph_key == self._graph_state():
