@@ -11,7 +11,7 @@ random-init model of a named architecture with synthetic prompt ids (no checkpoi
 
   python examples/generate.py --ckpt_dir /ckpt/8B --tokenizer_path /ckpt/tokenizer.model --is_llama3
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/generate.py --ckpt_dir /ckpt/70B ...
-  python examples/generate.py --synthetic --model llama3-8b --max_gen_len 32 [--weights fp8]
+  python examples/generate.py --synthetic --model llama3-8b --max_gen_len 32 [--weights fp8|mxfp4]
 """
 from __future__ import annotations
 
@@ -32,12 +32,14 @@ from jax_llama_amd.utils.checkpoint import load_meta_rank  # noqa: E402
 
 PROMPTS = ["The capital of Germany is the city of",
            "Here is my sonnet in the style of Shakespeare about an artificial intelligence:"]
+WEIGHT_FORMATS = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4"}  # --weights -> LLaMAForCausalLM.quantize_weights_
 
 
 def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int = 2048, weights: str = "bf16",
          kv_cache: str = "bf16", **model_kwargs) -> LLaMA:
-    """Reference ``load`` (jax_example.py:10-31) on the MI355X runtime. ``weights="fp8"``: the layer projections are
-    quantised to FP8 e4m3 after loading (``LLaMAForCausalLM.quantize_weights_``; each rank its own shard).
+    """Reference ``load`` (jax_example.py:10-31) on the MI355X runtime. ``weights="fp8"`` / ``"mxfp4"``: the layer
+    projections are quantised to FP8 e4m3 / MXFP4 after loading (``LLaMAForCausalLM.quantize_weights_``; each rank its
+    own shard).
     ``kv_cache="fp8"``: the KV caches hold FP8 e4m3 rows (``LLaMAForCausalLM.set_kv_cache_format``)."""
     ctx = init_distributed()
     ctx.setup_mesh(tp=ctx.world)
@@ -49,8 +51,8 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
     config.bos_token_id, config.eos_token_id = tokenizer.bos_id, tokenizer.eos_id
     model = LLaMAForCausalLM(config, device=ctx.device, comm=comm, _do_init=False, **model_kwargs).load_params(params, sharded=True)
     del params
-    if weights == "fp8":
-        model.quantize_weights_("fp8_e4m3")
+    if weights != "bf16":
+        model.quantize_weights_(WEIGHT_FORMATS[weights])
     if kv_cache == "fp8":
         model.set_kv_cache_format("fp8_e4m3")
     return LLaMA(None, model, tokenizer, mesh=Mesh(dp=1, mp=ctx.tp_size, rank=ctx.rank))
@@ -77,8 +79,8 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
     cfg = get_preset(model_name, max_seq_len=max(2048, prompt_len + max_gen_len))
     comm = TPComm.from_context(ctx, fused_hidden=cfg.hidden_size)
     model = LLaMAForCausalLM(cfg, device=ctx.device, comm=comm, _do_init=False).init_random(seed=0)
-    if weights == "fp8":
-        model.quantize_weights_("fp8_e4m3")
+    if weights != "bf16":
+        model.quantize_weights_(WEIGHT_FORMATS[weights])
     if kv_cache == "fp8":
         model.set_kv_cache_format("fp8_e4m3")
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
@@ -107,8 +109,9 @@ if __name__ == "__main__":
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--prompt_len", type=int, default=16)
-    ap.add_argument("--weights", choices=["bf16", "fp8"], default="bf16",
-                    help="fp8: FP8 e4m3 weight-only layer projections (one power-of-two scale per output row)")
+    ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
+                    help="fp8: FP8 e4m3 weight-only layer projections (one power-of-two scale per output row); "
+                    "mxfp4: 4-bit e2m1 codes with one power-of-two scale per row and 32 K elements")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: KV caches of FP8 e4m3 rows (one power-of-two scale per row, kv head and slot): 132 bytes "
                     "per 128-value row instead of 256")

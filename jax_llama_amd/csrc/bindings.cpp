@@ -354,6 +354,67 @@ void linear_qkv_w8(Tensor x, Tensor w8, Tensor scale, int64_t n, int64_t k, doub
      "linear_qkv_w8");
 }
 
+// ---- MXFP4 weight-only linears (gemv.hip): w4 uint8 [N/16, K/128, 64, 16] (two e2m1 codes per byte), s4 uint8
+// [N/16, K/128, 16, 4] (e8m0 bytes)
+void check_packed_w4(const Tensor& w4, const Tensor& s4, int64_t n, int64_t k) {
+  check_gpu(w4, "mxfp4 weight");
+  check_gpu(s4, "mxfp4 scale");
+  check(n > 0 && k > 0 && n % 16 == 0 && k % 128 == 0, "mxfp4 weight: N % 16 == 0, K % 128 == 0");
+  check(w4.scalar_type() == torch::kUInt8 && w4.dim() == 4 && w4.size(0) == n / 16 && w4.size(1) == k / 128 &&
+            w4.size(2) == 64 && w4.size(3) == 16,
+        "mxfp4 weight must be uint8 [N/16, K/128, 64, 16]");
+  check(s4.scalar_type() == torch::kUInt8 && s4.dim() == 4 && s4.size(0) == n / 16 && s4.size(1) == k / 128 &&
+            s4.size(2) == 16 && s4.size(3) == 4,
+        "mxfp4 scale must be uint8 [N/16, K/128, 16, 4]");
+  check(w4.device() == s4.device(), "mxfp4 weight and scale on one device");
+}
+
+// out = W_deq in the bf16 fragment-packed layout
+void dequant_fp4(Tensor w4, Tensor s4, int64_t n, int64_t k, Tensor out) {
+  check_packed_w4(w4, s4, n, k);
+  check_packed(out, n, k);
+  rc(jla::dequant_fp4(w4.data_ptr(), s4.data_ptr(), out.data_ptr(), n, k, stream()), "dequant_fp4");
+}
+
+// The plan of an MXFP4-weight decode-GEMV call, or the rule that refuses it (kernels/gemv_plan.h gemv_w4_plan)
+void skinny_w4_plan(int64_t m, int64_t n, int64_t k, int64_t mode, bool f32) {
+  const jla::GemvPlanResult r = jla::gemv_w4_plan((int)m, (int)n, (int)k, (int)mode, f32);
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: MXFP4-weight decode GEMV: ", r.why, " (see gemv_plan.h)");
+}
+
+void linear_skinny_w4(Tensor x, Tensor w4, Tensor s4, int64_t n, int64_t k, Tensor out, int64_t mode, double rms_eps,
+                      bool accumulate, c10::optional<Tensor> mirror, c10::optional<Tensor> pack_out) {
+  check_gpu(x, "x");
+  check_packed_w4(w4, s4, n, k);
+  check(x.dim() == 2 && x.size(1) == k, "x must be [M, K]");
+  check(mode >= 0 && mode <= 2, "linear_skinny_w4 mode");
+  const int64_t m = x.size(0);
+  skinny_w4_plan(m, n, k, mode, x.scalar_type() != torch::kBFloat16);
+  check_linear_out(out, m, n, mode);
+  jla::QKVArgs qa{};
+  qa.res_bf16 = mode == 1 ? mirror_ptr(mirror, out.numel()) : nullptr;
+  qa.pack = packed_ptr(pack_out, m, mode == 2 ? n / 2 : n, "pack_out");
+  check(!qa.pack || (mode == 1 || mode == 2), "pack_out: residual (mirror) or SwiGLU output only");
+  check(!qa.pack || mode != 1 || qa.res_bf16, "pack_out of a residual needs the mirror");
+  rc(jla::linear_skinny_w4(x.data_ptr(), 0, w4.data_ptr(), s4.data_ptr(), out.data_ptr(), m, n, k, mode,
+                           (float)rms_eps, accumulate, out.scalar_type() == torch::kFloat32, &qa, stream()),
+     "linear_skinny_w4");
+}
+
+void linear_qkv_w4(Tensor x, Tensor w4, Tensor s4, int64_t n, int64_t k, double rms_eps, Tensor table,
+                   Tensor positions, Tensor kc, Tensor vc, Tensor slot, int64_t seq_len, int64_t h, int64_t hkv,
+                   int64_t dh, Tensor q) {
+  check_gpu(x, "x");
+  check_packed_w4(w4, s4, n, k);
+  check(x.dim() == 2 && x.size(1) == k, "x must be [M, K]");
+  const int64_t m = x.size(0);
+  skinny_w4_plan(m, n, k, MODE_QKV, x.scalar_type() != torch::kBFloat16);
+  jla::QKVArgs qa = qkv_args(m, n, table, positions, kc, vc, slot, seq_len, h, hkv, dh, q);
+  rc(jla::linear_skinny_w4(x.data_ptr(), 0, w4.data_ptr(), s4.data_ptr(), nullptr, m, n, k, MODE_QKV, (float)rms_eps,
+                           0, 0, &qa, stream()),
+     "linear_qkv_w4");
+}
+
 // fused small-batch qkv projection + decode attention (gemv.hip qkv_attn_kernel): q [M, H, Dh] (scratch the
 // attention workgroups read), the attention output out [M, H * Dh] (+ its packed copy); splits from qkv_attn_splits
 void linear_qkv_attn(Tensor x, Tensor w, int64_t n, int64_t k, double rms_eps, Tensor table, Tensor positions,
@@ -1015,6 +1076,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
         py::arg("k"), py::arg("out"), py::arg("mode"), py::arg("rms_eps"), py::arg("accumulate"),
         py::arg("mirror") = py::none(), py::arg("pack_out") = py::none());
   m.def("linear_qkv_w8", &linear_qkv_w8, py::arg("x"), py::arg("w8"), py::arg("scale"), py::arg("n"), py::arg("k"),
+        py::arg("rms_eps"), py::arg("table"), py::arg("positions"), py::arg("kc"), py::arg("vc"), py::arg("slot"),
+        py::arg("seq_len"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("q"));
+  // (rc, mt, nt, nw) of an MXFP4-weight decode-GEMV call (kernels/gemv_plan.h gemv_w4_plan); rc != 0: the dequant path
+  m.def("gemv_w4_plan_check", [](int64_t m, int64_t n, int64_t k, int64_t mode, bool x_f32) {
+    const jla::GemvPlanResult r = jla::gemv_w4_plan((int)m, (int)n, (int)k, (int)mode, x_f32);
+    return py::make_tuple(r.rc, r.plan.mt, r.plan.nt, r.plan.nw);
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("mode"), py::arg("x_f32"));
+  m.def("dequant_fp4", &dequant_fp4, py::arg("w4"), py::arg("s4"), py::arg("n"), py::arg("k"), py::arg("out"));
+  m.def("linear_skinny_w4", &linear_skinny_w4, py::arg("x"), py::arg("w4"), py::arg("s4"), py::arg("n"),
+        py::arg("k"), py::arg("out"), py::arg("mode"), py::arg("rms_eps"), py::arg("accumulate"),
+        py::arg("mirror") = py::none(), py::arg("pack_out") = py::none());
+  m.def("linear_qkv_w4", &linear_qkv_w4, py::arg("x"), py::arg("w4"), py::arg("s4"), py::arg("n"), py::arg("k"),
         py::arg("rms_eps"), py::arg("table"), py::arg("positions"), py::arg("kc"), py::arg("vc"), py::arg("slot"),
         py::arg("seq_len"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("q"));
   m.def("gemv_variant_table", []() {  // {id: (packed x, split-K)}

@@ -1368,6 +1368,258 @@ int linear_skinny_w8(const void* x, int x_is_f32, const void* W8, const float* s
   return -1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// MXFP4 weight-only linears: W_deq[n, k] = value(code[n, k]) * 2^(s[n, k / 32] - 127): e2m1 codes (bit 3 the sign, bits
+// 2..0 index {0, 0.5, 1, 1.5, 2, 3, 4, 6}) with one e8m0 scale byte per output row and 32 consecutive K elements, so W_deq
+// is exact in bf16 and a quantised linear is the bf16 linear on W_deq. The codes are stored in 16(n) x 128(k) blocks
+// [N / 16][K / 128][64 lanes][16 bytes]: dword j of lane l of block (nt, kb) holds code[16 nt + (l & 15)][128 kb + 32 j
+// + 8 (l >> 4) + 0..7], two per byte with the lower k in the low nibble -- the element order of the bf16 B fragment of
+// k-step 4 kb + j. One 16-byte load per lane is 1 KiB per wave, as the bf16 layout, and feeds four MFMAs. The scales
+// are stored [N / 16][K / 128][16 rows][4]: one dword per (row, block), byte j the scale of k-step 4 kb + j; lane l
+// reads dword l & 15.
+
+// one dword of 8 e2m1 codes -> the 8 bf16 of one B fragment, times 2^(sbyte - 127): four v_cvt_scalef32_pk_bf16_fp4
+// whose fp32 scale operand is the e8m0 byte moved into the exponent field (a zero byte: 0.0, and code 0 converts to 0)
+JLA_DEV u32x4 fp4x8_to_bf16(unsigned q, unsigned sbyte) {
+  const float sc = __uint_as_float(sbyte << 23);
+  u32x4 r;
+  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 0));
+  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 1));
+  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 2));
+  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 3));
+  return r;
+}
+
+// Dequantise a packed MXFP4 weight into the bf16 fragment-packed layout (common.h): thread = one lane of one 16 x 128
+// block; reads its 16 bytes and its row's scale dword, writes its 16 bytes of fragments 4 kb .. 4 kb + 3. The
+// conversion applies the power-of-two scale exactly, so the output is bit-identical to pack_frag16x32(W_deq).
+__global__ void __launch_bounds__(256)
+    dequant_fp4_kernel(const u32x4* __restrict__ W4, const unsigned* __restrict__ S4, u32x4* __restrict__ out,
+                       long long lanes) {
+  const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (g >= lanes) return;
+  const int lane = (int)(g & 63);
+  const long long blk = g >> 6;  // nt * KB + kb
+  const u32x4 q = W4[g];
+  const unsigned sd = S4[blk * 16 + (lane & 15)];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    out[(4 * blk + j) * 64 + lane] = fp4x8_to_bf16(q[j], (sd >> (8 * j)) & 0xffu);  // fragment (nt, 4 kb + j)
+}
+
+int dequant_fp4(const void* W4, const void* S4, void* out, int N, int K, hipStream_t s) {
+  if (N <= 0 || K <= 0) return 0;
+  if ((N & 15) || (K & 127)) return -1;
+  const long long lanes = (long long)(N >> 4) * (K >> 7) * 64;
+  const long long grid = (lanes + 255) / 256;
+  if (grid > 0x7fffffffLL) return -1;
+  dequant_fp4_kernel<<<(int)grid, 256, 0, s>>>(static_cast<const u32x4*>(W4), static_cast<const unsigned*>(S4),
+                                              static_cast<u32x4*>(out), lanes);
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+// The MXFP4-weight GEMV body: linear_skinny_w8_kernel's workgroup (NT n-tiles x the whole K over NW waves, a register
+// ring of U slots, past-the-end refills from the zero fragment: code 0 at scale bits 0 converts to 0) with 128-deep K
+// blocks: wave w takes blocks w, w + NW, ...; one slot is, per n-tile, the weight load (1 KiB, non-temporal) and the
+// scale load (one dword per lane), plus the x fragments of the block's four k-steps. The weights are converted to bf16
+// in registers with the k-step's block scale as the instruction's scale operand, so nothing multiplies the accumulators
+// afterwards. KD = 2: a slot is half a block (two k-steps: the lane's 8 bytes of them, the same scale dword, half the x
+// fragments) and wave w streams half w & 1 of blocks w / 2, w / 2 + NW / 2, ... -- the four-m-tile forms, whose
+// 128-deep slots would hold 16 x-fragment loads. ASM: the hand-counted ring of skinny_body (ring.h;
+// tools/check_asm_ring.py checks it at build), built for one and two m-tiles (M <= 32); four m-tiles run
+// compiler-counted loads.
+template <int MT, int NT, int MODE, int NW, int U, bool ASM, int KD>
+__global__ void __launch_bounds__(NW * 64)
+    linear_skinny_w4_kernel(const bf16_t* __restrict__ x, const u32x4* __restrict__ W4, const unsigned* __restrict__ S4,
+                            void* __restrict__ out, int M, int N, int K, float eps, int use_rms, int accumulate,
+                            int out_f32, QKVArgs qa) {
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int KB = K >> 7;
+  const int NTT = N >> 4;
+  const int bx = blockIdx.x;
+  const int nt0 = bx * NT;
+
+  static_assert(KD == 4 || KD == 2, "a slot is a whole 128-deep block or half of one");
+  constexpr int PARTS = 4 / KD;    // slots per block
+  constexpr int NWB = NW / PARTS;  // waves that share one part: the wave's blocks are kb = wb + i * NWB
+  using WQ = std::conditional_t<KD == 4, u32x4, u32x2>;  // the lane's codes of one slot
+  const int wb = w / PARTS, part = w % PARTS;  // (wave-uniform)
+  const int sh = 8 * KD * part;                // the part's first scale byte in the block's dword
+
+  const WQ* wt[NT];
+  const unsigned* st[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int tile = min(nt0 + t, NTT - 1);  // (an odd tile count: the last workgroup re-reads the last tile, not stored)
+    wt[t] = reinterpret_cast<const WQ*>(W4 + (size_t)tile * KB * 64 + lane) + part;
+    st[t] = S4 + (size_t)tile * KB * 16 + (lane & 15);
+  }
+  const bf16_t* xp[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    const int row = min(mt * 16 + (lane & 15), M - 1);  // padding rows re-read the last row (not stored)
+    xp[mt] = x + (size_t)row * K + 8 * (lane >> 4) + 32 * KD * part;
+  }
+  const u32x4* zfrag = g_zero_frag + lane;
+  const bf16_t* zx = reinterpret_cast<const bf16_t*>(g_zero_frag);
+
+  const int n = (KB - wb + NWB - 1) / NWB;  // slots of this wave: its part of blocks kb = wb + i * NWB, i < n
+
+  f32x4 acc[MT][NT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float ss[MT];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) ss[mt] = 0.f;
+
+  WQ bq[U][NT] = {};
+  unsigned sq[U][NT] = {};
+  XRaw<bf16_t> aq[U][MT][KD] = {};
+  constexpr int L = 2 * NT + KD * MT;  // loads per ring slot
+  static_assert(!ASM || L * (U - 1) < 64, "vmcnt range");
+  auto issue = [&](int i, WQ* b, unsigned* sc, XRaw<bf16_t>(*a)[KD]) {
+    const bool valid = i < n;
+    const size_t kb = (size_t)(wb + i * NWB);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      asm_load_nt<ASM>(b[t], valid ? (const void*)(wt[t] + kb * 64 * PARTS) : (const void*)zfrag);
+      asm_load_b32<ASM>(sc[t], valid ? (const void*)(st[t] + kb * 16) : (const void*)zfrag);
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+      for (int j = 0; j < KD; ++j) a[mt][j].template load<ASM>(valid ? xp[mt] + kb * 128 + 32 * j : zx);
+  };
+  // (as skinny_body: no prologue, the first trip multiplies the zero-initialised slots while it issues blocks 0..U-1)
+  for (int i0 = -U; i0 < n; i0 += U) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      if constexpr (ASM) {
+        wait_vmcnt<L * (U - 1)>();  // slot u (the oldest L loads) has landed
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          pin(bq[u][t]);
+          pin(sq[u][t]);
+        }
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+          for (int j = 0; j < KD; ++j) aq[u][mt][j].pin_regs();
+      }
+#pragma unroll
+      for (int j = 0; j < KD; ++j) {
+        u32x4 af[MT];
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) af[mt] = aq[u][mt][j].frag(ss[mt]);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const u32x4 b = fp4x8_to_bf16(bq[u][t][j], (sq[u][t] >> (sh + 8 * j)) & 0xffu);
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) acc[mt][t] = mfma16x16x32(af[mt], b, acc[mt][t]);
+        }
+      }
+      issue(i0 + U + u, bq[u], sq[u], aq[u]);
+    }
+  }
+  if constexpr (ASM) {  // retire the past-the-end refills; every ring register stays live until then (skinny_body)
+    wait_vmcnt<0>();
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        pin(bq[u][t]);
+        pin(sq[u][t]);
+      }
+#pragma unroll
+      for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int j = 0; j < KD; ++j) aq[u][mt][j].pin_regs();
+    }
+  }
+
+  skinny_epilogue<MT, NT, MODE, NW, false, false>(acc, ss, 0, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, bx,
+                                                  0, 1);
+}
+
+// k-steps per ring slot of the form with `mt` m-tiles: the whole 128-deep block, or half of it at four m-tiles, where a
+// whole-block slot holds 16 x-fragment loads (64 registers): measured 1-10 % faster there (profiles/README.md, MXFP4)
+constexpr int W4_KD(int mt) { return mt == 4 ? 2 : 4; }
+
+template <int MT, int NT, int MODE, int NW>
+static int launch_skinny_w4(const void* x, const void* W4, const void* S4, void* out, int M, int N, int K, float eps,
+                            int use_rms, int accumulate, int out_f32, const QKVArgs& qa, hipStream_t s) {
+  // Slots in flight per wave. Whole-block slots hold the x registers of four k-steps (twice the FP8 kernel's), so the
+  // ring is half as many slots deep as launch_skinny_w8's at one tile and as deep at two; the half-block slots of four
+  // m-tiles: two, as the FP8 kernel's 64-deep ones. Hand-counted loads up to two m-tiles, as the FP8 kernel.
+  constexpr int KD = W4_KD(MT);
+  constexpr int U = (4 / MT) < 2 ? 2 : (4 / MT);
+  const int NTT = N >> 4;
+  const int grid = (NTT + NT - 1) / NT;
+  const size_t lds = sizeof(float) * (NW * MT * NT * 256 + NW * MT * 16 + MT * 16 + 4);
+  auto kern = &linear_skinny_w4_kernel<MT, NT, MODE, NW, U, (MT <= 2), KD>;
+  // (as launch_skinny_w8: once per process and instantiation, not per device -- a process that launched the four-m-tile,
+  // two-tile form on a second device would have to set it there too)
+  if (lds > 65536) {  // opt in to > 64 KiB of dynamic LDS once (not a stream op: capture-safe)
+    static bool attr_set = false;
+    if (!attr_set) {
+      hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      attr_set = true;
+    }
+  }
+  kern<<<grid, NW * 64, lds, s>>>(static_cast<const bf16_t*>(x), static_cast<const u32x4*>(W4),
+                                  static_cast<const unsigned*>(S4), out, M, N, K, eps, use_rms, accumulate, out_f32, qa);
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+// the one form a plan of gemv_w4_plan() names
+template <int MODE>
+static int launch_plan_w4(const void* x, const void* W4, const void* S4, void* out, int M, int N, int K, float eps,
+                          int use_rms, int accumulate, int out_f32, const QKVArgs& qa, const GemvPlan& p,
+                          hipStream_t s) {
+#define JLA_W4(MT, NT, NW)                                                                                            \
+  if (p.mt == MT && p.nt == NT && p.nw == NW)                                                                         \
+  return launch_skinny_w4<MT, NT, MODE, NW>(x, W4, S4, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, s)
+  if constexpr (MODE != MODE_SWIGLU) {
+    JLA_W4(1, 1, 4);
+    JLA_W4(2, 1, 8);
+    JLA_W4(4, 1, 8);
+  }
+  if constexpr (MODE != MODE_QKV) {
+    JLA_W4(1, 2, 4);
+    JLA_W4(2, 2, 8);
+    JLA_W4(4, 2, 8);
+  }
+#undef JLA_W4
+  return -1;  // (not a plan of gemv_w4_plan())
+}
+
+int linear_skinny_w4(const void* x, int x_is_f32, const void* W4, const void* S4, void* out, int M, int N, int K,
+                     int mode, float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, hipStream_t s) {
+  const GemvPlanResult r = gemv_w4_plan(M, N, K, mode, x_is_f32 != 0);
+  if (r.rc != 0 || r.plan.mt == 0) return r.rc;
+  if (mode == MODE_QKV && (!qkv || qkv->Dh % 16 || M % qkv->S)) return -1;
+  const int use_rms = rms_eps >= 0.f;
+  const float eps = use_rms ? rms_eps : 0.f;
+  QKVArgs qa{};
+  if (qkv) qa = *qkv;
+  switch (mode) {
+    case MODE_STORE:
+      return launch_plan_w4<MODE_STORE>(x, W4, S4, out, M, N, K, eps, use_rms, accumulate, out_f32, qa, r.plan, s);
+    case MODE_RESIDUAL:
+      return launch_plan_w4<MODE_RESIDUAL>(x, W4, S4, out, M, N, K, eps, use_rms, accumulate, 1, qa, r.plan, s);
+    case MODE_SWIGLU:
+      return launch_plan_w4<MODE_SWIGLU>(x, W4, S4, out, M, N, K, eps, use_rms, accumulate, 0, qa, r.plan, s);
+    case MODE_QKV:
+      return launch_plan_w4<MODE_QKV>(x, W4, S4, out, M, N, K, eps, use_rms, accumulate, 0, qa, r.plan, s);
+  }
+  return -1;
+}
+
 JLA_BOUNDS_ACCESSOR(gemv)
 
 }  // namespace jla

@@ -148,4 +148,24 @@ inline GemvPlanResult gemv_w8_plan(int M, int N, int K, int mode, bool x_f32) {
   return {0, "", p};
 }
 
+// The plan of one MXFP4-weight decode-GEMV call (gemv.hip linear_skinny_w4: e2m1 codes in 16 x 128 blocks, one e8m0
+// scale byte per output row and 32 consecutive K elements). The twin of gemv_w8_plan(): one form per (m-tiles,
+// epilogue), the tiles and waves of the default form, row-major bf16 x, no K split; K in whole 128-deep blocks (one
+// 16-byte lane load holds four k-steps). Whatever this refuses runs on the bf16 kernels over the dequantised weight.
+inline GemvPlanResult gemv_w4_plan(int M, int N, int K, int mode, bool x_f32) {
+  const auto fail = [](const char* why) { return GemvPlanResult{-1, why, GemvPlan{}}; };
+  if (mode != MODE_STORE && mode != MODE_RESIDUAL && mode != MODE_SWIGLU && mode != MODE_QKV)
+    return fail("the MXFP4-weight GEMV: store, residual, SwiGLU and qkv epilogues only");
+  if (x_f32) return fail("the MXFP4-weight GEMV reads bf16 activations");
+  if (M <= 0) return {0, "", GemvPlan{}};
+  if (M > SKINNY_MAX_M || (N & 15) || (K & 127)) return fail("shape: M <= 64, N % 16 == 0, K % 128 == 0");
+  if (mode == MODE_SWIGLU && (N & 31)) return fail("SwiGLU: N % 32 == 0");
+  GemvPlan p{};
+  p.mt = gemv_m_tiles(M);
+  p.nt = mode == MODE_SWIGLU || (mode != MODE_QKV && (N >> 4) >= 2048) ? 2 : 1;
+  p.nw = p.mt == 1 ? 4 : 8;
+  p.ksplit = 1;
+  return {0, "", p};
+}
+
 }  // namespace jla

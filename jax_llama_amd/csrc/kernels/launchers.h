@@ -86,6 +86,15 @@ int linear_skinny(const void* x, int x_is_f32, const void* W, void* out, int M, 
 int dequant_fp8(const void* W8, const float* scale, void* out, int N, int K, hipStream_t s);
 int linear_skinny_w8(const void* x, int x_is_f32, const void* W8, const float* scale, void* out, int M, int N, int K,
                      int mode, float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, hipStream_t s);
+// MXFP4 weight-only linears (gemv.hip): W4 is the e2m1 codes in 16 x 128 blocks [N / 16][K / 128][64 lanes][16 bytes]
+// (two codes per byte, the lower k in the low nibble), S4 the e8m0 scale bytes [N / 16][K / 128][16 rows][4 k-steps]
+// (W_deq = value(code) * 2^(byte - 127), exact in bf16). N % 16 == 0, K % 128 == 0.
+// dequant_fp4: out = W_deq in the bf16 fragment-packed layout [N / 16][K / 32][64][8].
+// linear_skinny_w4: the decode GEMV on the codes, y = epilogue(x @ W_deq^T), for the calls gemv_w4_plan() (gemv_plan.h)
+// accepts; -1 is its code. qkv as linear_skinny.
+int dequant_fp4(const void* W4, const void* S4, void* out, int N, int K, hipStream_t s);
+int linear_skinny_w4(const void* x, int x_is_f32, const void* W4, const void* S4, void* out, int M, int N, int K,
+                     int mode, float rms_eps, int accumulate, int out_f32, const QKVArgs* qkv, hipStream_t s);
 int clock_probe(int iters, int grid, unsigned long long* out, hipStream_t s);  // [cycles, 100 MHz ticks]
 // Tiled MFMA GEMM (gemm.hip): y = epilogue(x[M, K] @ W[N, K]^T) on the kernel the tile id names (gemm_plan.h: the
 // tile table, and gemm_plan(), every rule of a legal call; the return codes -1 / -5 / -6 / -7 are its). ksplit > 1

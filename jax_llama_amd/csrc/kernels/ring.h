@@ -23,6 +23,13 @@ JLA_DEV void asm_load_nt(u32x4& r, const void* p) {
     r = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
 }
 template <bool ASM>
+JLA_DEV void asm_load_nt(u32x2& r, const void* p) {  // 8 bytes per lane (the MXFP4 GEMV's half-block slots)
+  if constexpr (ASM)
+    asm volatile("global_load_dwordx2 %0, %1, off nt" : "+v"(r) : "v"(p) : "memory");
+  else
+    r = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+}
+template <bool ASM>
 JLA_DEV void asm_load(u32x4& r, const void* p) {
   if constexpr (ASM)
     asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(r) : "v"(p) : "memory");
@@ -35,6 +42,14 @@ JLA_DEV void asm_load16(u32x4& r, const void* p) {
     asm volatile("global_load_dwordx4 %0, %1, off offset:16" : "+v"(r) : "v"(p) : "memory");
   else
     r = reinterpret_cast<const u32x4*>(p)[1];
+}
+// one dword per lane (the MXFP4 GEMV's block scales)
+template <bool ASM>
+JLA_DEV void asm_load_b32(unsigned& r, const void* p) {
+  if constexpr (ASM)
+    asm volatile("global_load_dword %0, %1, off" : "+v"(r) : "v"(p) : "memory");
+  else
+    r = *reinterpret_cast<const unsigned*>(p);
 }
 // agent-coherent (sc1) load: bypasses the caches that can hold a stale copy of a line another
 // workgroup of the same launch wrote write-through (in-launch hand-offs, Guideline 16 R1)
@@ -63,6 +78,8 @@ JLA_DEV void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"i"(N) : "memory");
 }
 JLA_DEV void pin(u32x4& r) { asm volatile("" : "+v"(r)); }
+JLA_DEV void pin(unsigned& r) { asm volatile("" : "+v"(r)); }
+JLA_DEV void pin(u32x2& r) { asm volatile("" : "+v"(r)); }
 
 template <typename XT>
 struct XRaw;

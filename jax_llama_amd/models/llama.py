@@ -34,7 +34,7 @@ from ..parallel.comm import NO_COMM, TPComm
 from ..parallel.partition import shard_tree
 from .kv_cache import KV_FORMATS, KVCache
 from .modules import LLaMABlockCollection
-from .weights import Fp8Linear, PackedLinear
+from .weights import Fp8Linear, Mxfp4Linear, PackedLinear
 
 BF16 = torch.bfloat16
 
@@ -321,31 +321,49 @@ class LLaMAForCausalLM:
         from ..utils.native_ckpt import from_pretrained
         return from_pretrained(directory, device=device, comm=comm)
 
-    WEIGHT_FORMATS = ("fp8_e4m3",)
+    WEIGHT_FORMATS = ("fp8_e4m3", "mxfp4")
 
     def quantize_weights_(self, fmt: str = "fp8_e4m3") -> "LLaMAForCausalLM":
-        """Replace ``qkv``, ``o``, ``gu`` and ``down`` of every layer by FP8 (OCP e4m3fn) weight-only linears
-        (``models.weights.Fp8Linear``: one power-of-two scale per output row), in place, on either device. Runs after
-        the norm fold and the TP sharding, so each rank quantises its own shard. ``wte``, ``lm_head`` and
-        ``lm_head_f32`` keep their format. The model then computes exactly what a bf16 model loaded with the
-        dequantised weights computes op for op; decode batches up to 64 rows stream the fp8 bytes, larger calls pay
-        one dequant pass per projection. Calling it twice is an error."""
+        """Replace ``qkv``, ``o``, ``gu`` and ``down`` of every layer by weight-only quantised linears, in place, on
+        either device: ``"fp8_e4m3"`` (``models.weights.Fp8Linear``: OCP e4m3fn, one power-of-two scale per output row)
+        or ``"mxfp4"`` (``models.weights.Mxfp4Linear``: e2m1 codes with one e8m0 scale per output row and 32 K elements,
+        4.25 bits per weight; every projection needs N % 16 == 0 and K % 128 == 0, else ``ValueError`` and the model is
+        left as it was). Runs after the norm fold and the TP sharding, so each rank quantises its own shard; a K shard
+        is a multiple of 32, so the MXFP4 blocks of a shard are blocks of the whole matrix and quantise-then-shard and
+        shard-then-quantise give the same codes. ``wte``, ``lm_head`` and ``lm_head_f32`` keep their format. The model
+        then computes exactly what a bf16 model loaded with the dequantised weights computes op for op; decode batches
+        up to 64 rows stream the quantised bytes, larger calls pay one dequant pass per projection. Calling it twice is
+        an error. The cached decode engines of this model (``runtime.engine``) are dropped: they hold graphs captured
+        on the weights this call frees."""
         if fmt not in self.WEIGHT_FORMATS:
             raise ValueError(f"quantize_weights_: unknown format {fmt!r} (one of {self.WEIGHT_FORMATS})")
         if self.weight_format != "bf16":
             raise RuntimeError(f"quantize_weights_: the weights are already {self.weight_format}")
         if any(lw.qkv is None for lw in self.layers):
             raise RuntimeError("quantize_weights_: the model has no weights yet")
+        names = ("qkv", "o", "gu", "down")
+        if fmt == "mxfp4":  # (refuse before the first replacement: no half-quantised model)
+            for lw in self.layers:
+                for name in names:
+                    lin = getattr(lw, name)
+                    if lin.n % 16 or lin.k % 128:
+                        raise ValueError(f"quantize_weights_('mxfp4'): {name} is {lin.n}x{lin.k}; MXFP4 linear weights "
+                                         "need N % 16 == 0 and K % 128 == 0")
+        cls = Mxfp4Linear if fmt == "mxfp4" else Fp8Linear
         for lw in self.layers:
-            for name in ("qkv", "o", "gu", "down"):
-                setattr(lw, name, Fp8Linear.from_linear(getattr(lw, name)))
+            for name in names:
+                setattr(lw, name, cls.from_linear(getattr(lw, name)))
+        from ..runtime.engine import drop_engines
+        drop_engines(self)
         if self.device.type == "cuda":
             torch.cuda.empty_cache()
         return self
 
     @property
     def weight_format(self) -> str:
-        """``"bf16"``, or ``"fp8_e4m3"`` after ``quantize_weights_``."""
+        """``"bf16"``, or ``"fp8_e4m3"`` / ``"mxfp4"`` after ``quantize_weights_``."""
+        if any(getattr(lw.qkv, "mxfp4", False) for lw in self.layers):
+            return "mxfp4"
         return "fp8_e4m3" if any(getattr(lw.qkv, "fp8", False) for lw in self.layers) else "bf16"
 
     def weight_bytes(self) -> int:

@@ -260,8 +260,12 @@ def packed_empty(m: int, cols: int, device) -> torch.Tensor:
 # tuner is never asked). Every other call first dequantises the weight into a bf16 workspace (``bf16_weight``) and
 # runs the existing bf16 kernel on it unchanged: W_deq is exact in bf16, so that is the same kernel on the same bits
 # as a PackedLinear of W_deq, plus one dequant pass per call.
+#
+# MXFP4 weight-only linears (models.weights.Mxfp4Linear) route the same way: ``_w4_fast`` (gemv_w4_plan()) picks the
+# MXFP4 decode GEMV on the codes and block scales, every other call runs the bf16 kernel on ``dequant_fp4``'s copy.
 class _Dequantized:
-    """What the bf16 kernels read of an Fp8Linear: ``weight`` (fragment-packed bf16 workspace), ``n``, ``k``."""
+    """What the bf16 kernels read of an Fp8Linear / Mxfp4Linear: ``weight`` (fragment-packed bf16 workspace), ``n``,
+    ``k``."""
 
     def __init__(self, weight, n, k):
         self.weight, self.n, self.k = weight, n, k
@@ -271,11 +275,24 @@ def is_fp8(w) -> bool:
     return bool(getattr(w, "fp8", False))
 
 
+def is_mxfp4(w) -> bool:
+    return bool(getattr(w, "mxfp4", False))
+
+
+def is_quantized(w) -> bool:
+    """An ``Fp8Linear`` or an ``Mxfp4Linear``: the kernels that read bf16 fragments only decline it."""
+    return is_fp8(w) or is_mxfp4(w)
+
+
 def bf16_weight(w):
     """The weight the bf16 kernels read. A ``PackedLinear``: itself (no kernel, launch or allocation added). An
-    ``Fp8Linear``: ``W_deq`` dequantised (``dequant_fp8``) into the workspace keyed by its shape, so two weights one
-    launch reads never share a buffer; sized in the eager warm-up step like every workspace (nothing allocates under
-    graph capture)."""
+    ``Fp8Linear`` / ``Mxfp4Linear``: ``W_deq`` dequantised (``dequant_fp8`` / ``dequant_fp4``) into the workspace keyed
+    by its shape, so two weights one launch reads never share a buffer; sized in the eager warm-up step like every
+    workspace (nothing allocates under graph capture)."""
+    if is_mxfp4(w):
+        buf = workspace.get(f"w4_deq_{w.n}x{w.k}", w.n * w.k, BF16, w.device).view(w.n // 16, w.k // 32, 64, 8)
+        ext().dequant_fp4(w.qweight, w.scale, w.n, w.k, buf)
+        return _Dequantized(buf, w.n, w.k)
     if not is_fp8(w):
         return w
     buf = workspace.get(f"w8_deq_{w.n}x{w.k}", w.n * w.k, BF16, w.device).view(w.n // 16, w.k // 32, 64, 8)
@@ -288,11 +305,22 @@ def _w8_fast(e, x, w, mode) -> bool:
     return x.shape[0] > 0 and e.gemv_w8_plan_check(x.shape[0], w.n, w.k, mode, x.dtype != BF16)[0] == 0
 
 
+def _w4_fast(e, x, w, mode) -> bool:
+    """Whether this call on an ``Mxfp4Linear`` runs the MXFP4 decode GEMV (else the dequant path)."""
+    return x.shape[0] > 0 and e.gemv_w4_plan_check(x.shape[0], w.n, w.k, mode, x.dtype != BF16)[0] == 0
+
+
 def _gpu_linear(x, w, out, mode, rms_eps, accumulate, mirror=None, x_packed=None, pack_out=None):
     assert x.is_contiguous() and out.is_contiguous()
     assert x.shape[1] == w.k, (x.shape, w.k)
     m = x.shape[0]
     e = ext()
+    if is_mxfp4(w):
+        if _w4_fast(e, x, w, mode):
+            e.linear_skinny_w4(x, w.qweight, w.scale, w.n, w.k, out, mode, -1.0 if rms_eps is None else float(rms_eps),
+                               bool(accumulate), mirror, pack_out if mode != MODE_STORE else None)
+            return
+        w = bf16_weight(w)
     if is_fp8(w):
         if _w8_fast(e, x, w, mode):
             e.linear_skinny_w8(x, w.qweight, w.scale, w.n, w.k, out, mode, -1.0 if rms_eps is None else float(rms_eps),
@@ -503,9 +531,17 @@ def linear_qkv_rope(x: torch.Tensor, w, rms_eps: Optional[float], table: torch.T
     e = ext()
     if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
         # FP8 KV cache: always a plain store and the quantising write kernel (the rows that get quantised are defined
-        # from the bf16 projection output; no RoPE epilogue quantises), bf16 and Fp8Linear weights alike
+        # from the bf16 projection output; no RoPE epilogue quantises), bf16, Fp8Linear and Mxfp4Linear weights alike
         qkv = linear(x, w, rms_eps=rms_eps, x_packed=x_packed if m <= e.SKINNY_MAX_M else None)
         return rope_kv_write(qkv, table, positions, k_cache, v_cache, slot0, seq_len, n_heads, n_kv_heads, head_dim)
+    if is_mxfp4(w):
+        if _w4_fast(e, x, w, MODE_QKV):
+            q = torch.empty(m, n_heads, head_dim, dtype=BF16, device=x.device)
+            e.linear_qkv_w4(x, w.qweight, w.scale, w.n, w.k, -1.0 if rms_eps is None else float(rms_eps), table,
+                            positions.reshape(-1).to(torch.int32), k_cache, v_cache, _slot_tensor(slot0, x.device),
+                            int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q)
+            return q
+        w = bf16_weight(w)
     if is_fp8(w):
         if _w8_fast(e, x, w, MODE_QKV):
             q = torch.empty(m, n_heads, head_dim, dtype=BF16, device=x.device)
@@ -599,7 +635,7 @@ def _num_cus(device) -> int:
 def qkv_attention_o_groups(x: torch.Tensor, w_o, n_heads: int, n_kv_heads: int, k_cache=None) -> int:
     """Workgroups of the o projection when the fused decode launch can also run it (``linear_qkv_attention(o=...)``),
     else 0 (always 0 with an ``Fp8KV`` cache: the fused launch reads and writes bf16 caches only)."""
-    if not QKV_ATTN_O or not _is_gpu(x) or is_fp8(w_o) or is_fp8_kv(k_cache):
+    if not QKV_ATTN_O or not _is_gpu(x) or is_quantized(w_o) or is_fp8_kv(k_cache):
         return 0
     return int(ext().qkv_attn_o_groups(x.shape[0], n_heads // n_kv_heads, w_o.n, w_o.k))
 
@@ -609,8 +645,8 @@ def qkv_attention_splits(x: torch.Tensor, w, k_cache: torch.Tensor, seq_len: int
     """Attention workgroups per (row, kv head) pair of the fused qkv + attention launch for this decode step, or 0
     when it does not apply (prefill, a key mask, M > 32, a cache longer than 512, or a grid the CUs cannot hold at
     once). ``o_groups``: the launch also holds the o projection's workgroups (``qkv_attention_o_groups``)."""
-    if not QKV_ATTN or seq_len != 1 or key_mask is not None or not _is_gpu(x) or x.dtype != BF16 or is_fp8(w):
-        return 0  # (an Fp8Linear: the fused launch reads bf16 fragments only)
+    if not QKV_ATTN or seq_len != 1 or key_mask is not None or not _is_gpu(x) or x.dtype != BF16 or is_quantized(w):
+        return 0  # (an Fp8Linear / Mxfp4Linear: the fused launch reads bf16 fragments only)
     if is_fp8_kv(k_cache):
         return 0  # (an Fp8KV: the fused launch reads and writes bf16 caches only)
     m = x.shape[0]

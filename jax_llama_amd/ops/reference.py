@@ -188,6 +188,121 @@ def unpack_fp8_16x64(p: torch.Tensor, n: int, k: int) -> torch.Tensor:
 
 
 # ----------------------------------------------------------------------------------
+# MXFP4 weight-only quantisation: e2m1 codes, one e8m0 (power-of-two) scale per output row and 32 K elements
+# ----------------------------------------------------------------------------------
+MXFP4_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitudes of codes 0..7; bit 3 of a code is the sign
+MXFP4_EXP_CLAMP = 100
+E8M0_BIAS = 127
+
+
+def e2m1_rne(v: torch.Tensor) -> torch.Tensor:
+    """fp32 values -> e2m1 codes (uint8, 0..15): round to nearest, ties to the even code (the tie points 0.25 / 0.75 /
+    1.25 / 1.75 / 2.5 / 3.5 / 5 go to 0 / 1 / 1 / 2 / 2 / 4 / 4), saturating at 6; the sign bit is the input's (also
+    of -0.0)."""
+    a = v.abs()
+    mag = ((a > 0.25).to(torch.uint8) + (a >= 0.75).to(torch.uint8) + (a > 1.25).to(torch.uint8)
+           + (a >= 1.75).to(torch.uint8) + (a > 2.5).to(torch.uint8) + (a >= 3.5).to(torch.uint8)
+           + (a > 5.0).to(torch.uint8))
+    return mag | (torch.signbit(v).to(torch.uint8) << 3)
+
+
+def quantize_mxfp4(w: torch.Tensor):
+    """``[N, K]`` weight (K % 32 == 0) -> ``(codes uint8 [N, K] in 0..15, e8m0 uint8 [N, K/32])``. The storage format is
+    OCP MX (e2m1 elements, one e8m0 scale ``2^(b - 127)`` per 32 consecutive K elements of a row); the scale rule is
+    the one of ``quantize_fp8_rows`` with 6 in place of 448 and a block in place of a row: ``e = ceil(log2(amax_block /
+    6))`` clamped to [-100, 100] (0 for an all-zero block), ``code = e2m1_rne(w / 2^e)``. Nothing saturates except
+    where the clamp acted -- unlike OCP's ``floor`` rule, which can clip the block maximum.
+
+    The exponent comes from ``frexp`` (no rounded logarithm): ``amax = m 2^x`` with ``m`` in [0.5, 1) and
+    ``6 = 0.75 * 2^3``, so ``e = x - 3`` where ``m <= 0.75`` and ``x - 2`` above."""
+    if w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise ValueError(f"quantize_mxfp4: a [N, K] matrix with K % 32 == 0, got {tuple(w.shape)}")
+    n, k = w.shape
+    wf = w.float().reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = wf.abs().amax(2)
+    m, x = torch.frexp(amax)
+    e = torch.where(m <= 0.75, x - 3, x - 2)
+    e = torch.where(amax == 0, torch.zeros_like(e), e).clamp(-MXFP4_EXP_CLAMP, MXFP4_EXP_CLAMP)
+    scale = torch.ldexp(torch.ones_like(amax), e)
+    codes = e2m1_rne(wf / scale[:, :, None]).reshape(n, k)
+    return codes, (e + E8M0_BIAS).to(torch.uint8)
+
+
+def dequantize_mxfp4(codes: torch.Tensor, e8m0: torch.Tensor) -> torch.Tensor:
+    """``W_deq = value(code) * 2^(e8m0 - 127)`` as bf16 ``[N, K]`` (exact: three significant bits times a power of
+    two)."""
+    n, k = codes.shape
+    lut = torch.tensor(E2M1_VALUES + tuple(-v for v in E2M1_VALUES), dtype=torch.float32, device=codes.device)
+    val = lut[codes.long()].reshape(n, k // MXFP4_BLOCK, MXFP4_BLOCK)
+    scale = torch.ldexp(torch.ones(e8m0.shape, dtype=torch.float32, device=codes.device),
+                        e8m0.to(torch.int32) - E8M0_BIAS)
+    return (val * scale.reshape(n, k // MXFP4_BLOCK, 1)).reshape(n, k).to(BF16)
+
+
+def _check_mxfp4_shape(n: int, k: int):
+    if n <= 0 or k <= 0 or n % 16 or k % 128:
+        raise ValueError(f"MXFP4 linear weights need N % 16 == 0 and K % 128 == 0, got {n}x{k}")
+
+
+def pack_mxfp4_16x128(codes: torch.Tensor) -> torch.Tensor:
+    """``[N, K]`` e2m1 codes (uint8, 0..15) -> uint8 ``[N/16, K/128, 64 lanes, 16 bytes]``: lane ``l`` of block
+    ``(nt, kb)`` owns row ``16 nt + (l & 15)``, and its dword ``j`` (bytes ``4 j .. 4 j + 3``) holds the eight codes at
+    ``k = 128 kb + 32 j + 8 (l >> 4) + 0..7``, two per byte -- the element order of the bf16 fragment of k-step
+    ``4 kb + j`` (``pack_frag16x32``). The lower ``k`` of a byte is in the LOW nibble: byte ``i`` of a dword is the
+    pair the conversion instruction's byte select ``i`` turns into one packed bf16 pair, low nibble first (settled by
+    the GPU dequant kernel's bit-equality test against ``pack_frag16x32(W_deq)``)."""
+    if codes.dim() != 2:
+        raise ValueError(f"pack_mxfp4_16x128: a [N, K] matrix, got {tuple(codes.shape)}")
+    n, k = codes.shape
+    _check_mxfp4_shape(n, k)
+    if codes.dtype != torch.uint8:
+        raise ValueError(f"pack_mxfp4_16x128: uint8 codes, got {codes.dtype}")
+    c = codes.reshape(n // 16, 16, k // 128, 4, 4, 4, 2)  # [nt, row, kb, j, l >> 4, byte, nibble]
+    b = (c[..., 0] & 15) | (c[..., 1] << 4)
+    return b.permute(0, 2, 4, 1, 3, 5).contiguous().reshape(n // 16, k // 128, 64, 16)
+
+
+def unpack_mxfp4_16x128(p: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """Inverse of ``pack_mxfp4_16x128``: the ``[n, k]`` codes."""
+    _check_mxfp4_shape(n, k)
+    if p.dtype != torch.uint8 or p.numel() != n * k // 2:
+        raise ValueError(f"unpack_mxfp4_16x128: uint8 with {n * k // 2} bytes, got {p.dtype} {tuple(p.shape)}")
+    b = p.reshape(n // 16, k // 128, 4, 16, 4, 4).permute(0, 3, 1, 4, 2, 5)  # [nt, row, kb, j, l >> 4, byte]
+    return torch.stack([b & 15, b >> 4], -1).contiguous().reshape(n, k)
+
+
+def pack_mxfp4_scales(e8m0: torch.Tensor) -> torch.Tensor:
+    """``[N, K/32]`` e8m0 bytes -> uint8 ``[N/16, K/128, 16 rows, 4]``: one dword per (row, 128-deep block), byte ``j``
+    the scale of k-step ``4 kb + j``; lane ``l`` of the block reads dword ``l & 15`` (64 bytes per block)."""
+    if e8m0.dim() != 2:
+        raise ValueError(f"pack_mxfp4_scales: a [N, K/32] matrix, got {tuple(e8m0.shape)}")
+    n, k = e8m0.shape[0], e8m0.shape[1] * MXFP4_BLOCK
+    _check_mxfp4_shape(n, k)
+    if e8m0.dtype != torch.uint8:
+        raise ValueError(f"pack_mxfp4_scales: uint8 scale bytes, got {e8m0.dtype}")
+    return e8m0.reshape(n // 16, 16, k // 128, 4).permute(0, 2, 1, 3).contiguous()
+
+
+def unpack_mxfp4_scales(p: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """Inverse of ``pack_mxfp4_scales``: the ``[n, k/32]`` e8m0 bytes."""
+    _check_mxfp4_shape(n, k)
+    if p.dtype != torch.uint8 or p.numel() != n * k // MXFP4_BLOCK:
+        raise ValueError(f"unpack_mxfp4_scales: uint8 with {n * k // MXFP4_BLOCK} bytes, got {p.dtype} {tuple(p.shape)}")
+    return p.reshape(n // 16, k // 128, 16, 4).permute(0, 2, 1, 3).contiguous().reshape(n, k // MXFP4_BLOCK)
+
+
+def nibble_pairs(codes: torch.Tensor) -> torch.Tensor:
+    """``[N, K]`` codes -> uint8 ``[N, K/2]`` in natural order, the even ``k`` in the low nibble (the checkpoint form)."""
+    return (codes[:, 0::2] & 15) | (codes[:, 1::2] << 4)
+
+
+def nibble_unpairs(b: torch.Tensor) -> torch.Tensor:
+    """Inverse of ``nibble_pairs``."""
+    return torch.stack([b & 15, b >> 4], -1).reshape(b.shape[0], 2 * b.shape[1])
+
+
+# ----------------------------------------------------------------------------------
 # Elementwise / normalisation
 # ----------------------------------------------------------------------------------
 def embedding(ids: torch.Tensor, table: torch.Tensor) -> torch.Tensor:

@@ -149,8 +149,9 @@ class TPComm:
         done) otherwise -- the caller then runs ``linear`` + ``all_reduce_residual_``."""
         f = self.fused
         if (f is None or self.size == 1 or self.reduce_dtype != torch.bfloat16 or not x.is_cuda
-                or x.dtype != torch.bfloat16 or getattr(w, "fp8", False)):
-            return False  # (an Fp8Linear: the unfused partial + collective path; the fused epilogues read bf16 weights)
+                or x.dtype != torch.bfloat16 or (getattr(w, "fp8", False) or getattr(w, "mxfp4", False))):
+            # (an Fp8Linear / Mxfp4Linear: the unfused partial + collective path; the fused epilogues read bf16 weights)
+            return False
         m = x.shape[0]
         if f.can_fuse(m, w.n):
             f.linear_residual_(x, w, h, hb, x_packed=x_packed, hb_pack=hb_pack)
@@ -168,7 +169,7 @@ class TPComm:
             return 0
         f = self.fused
         if (f is None or self.reduce_dtype != torch.bfloat16 or not x.is_cuda or x.dtype != torch.bfloat16
-                or getattr(w, "fp8", False) or not f.can_fuse(x.shape[0], w.n)):
+                or (getattr(w, "fp8", False) or getattr(w, "mxfp4", False)) or not f.can_fuse(x.shape[0], w.n)):
             return None
         return f._live()
 

@@ -361,6 +361,15 @@ def _engine_budget(model) -> int:
     return 8 << 30
 
 
+def drop_engines(model) -> int:
+    """Forget every cached engine of ``model`` (``quantize_weights_`` calls it: an engine's captured decode graph holds
+    the addresses of the weights it was captured on). Returns how many were dropped."""
+    keys = [k for k in _ENGINES if k[0] == id(model)]
+    for k in keys:
+        del _ENGINES[k]
+    return len(keys)
+
+
 def get_engine(model, batch_size: int, max_length: int) -> DecodeEngine:
     """Per-(model, B, max_length) engines (each owns a KV cache and a captured decode graph), kept in
     LRU order and bounded by the bytes of their KV caches. The model's KV-cache format is part of the key: an engine

@@ -1,12 +1,14 @@
 #!/usr/bin/env python3
-"""FP8-weight decode GEMV against the bf16 decode GEMV (default form, variant 1) at the layer shapes of a model.
+"""FP8-weight and MXFP4-weight decode GEMVs against the bf16 decode GEMV (default form, variant 1) at the layer shapes of
+a model.
 
-One process, interleaved: per (projection, M) the two kernels are captured into one hipGraph each (decode GEMVs run
+One process, interleaved: per (projection, M) the kernels are captured into one hipGraph each (decode GEMVs run
 below the host's launch rate) over weight copies that rotate through more than twice the 256 MiB Infinity Cache, so
 every call streams from HBM; the graphs are replayed alternately for ``--rounds`` rounds. One JSON line per point:
-microseconds (min and median of the rounds) and effective TB/s of each kernel, and bf16 / fp8 (> 1: fp8 is faster).
+microseconds (min and median of the rounds) and effective TB/s of each kernel (its own bytes over its own time), and
+bf16 / fp8, bf16 / mxfp4 and fp8 / mxfp4 (> 1: the second is faster).
 
-  python tools/bench_gemv_w8.py [--model llama3-8b] [--m 1 16 64] [--rounds 9]
+  python tools/bench_gemv_w8.py [--model llama3-8b] [--m 1 16 64] [--rounds 9] [--formats bf16 fp8 mxfp4]
 """
 from __future__ import annotations
 
@@ -22,7 +24,7 @@ import torch  # noqa: E402
 
 from jax_llama_amd import ops  # noqa: E402
 from jax_llama_amd.config import get_preset  # noqa: E402
-from jax_llama_amd.models.weights import Fp8Linear, PackedLinear  # noqa: E402
+from jax_llama_amd.models.weights import Fp8Linear, Mxfp4Linear, PackedLinear  # noqa: E402
 
 DEV = "cuda"
 BF16 = torch.bfloat16
@@ -34,6 +36,7 @@ def main():
     ap.add_argument("--m", type=int, nargs="+", default=[1, 16, 64])
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--ops", nargs="+", default=None, help="subset of qkv o gate_up down")
+    ap.add_argument("--formats", nargs="+", choices=["bf16", "fp8", "mxfp4"], default=["bf16", "fp8", "mxfp4"])
     args = ap.parse_args()
     cfg = get_preset(args.model)
     d, f, hd = cfg.hidden_size, cfg.intermediate_size, cfg.head_dim
@@ -43,9 +46,17 @@ def main():
     for name, (n, k, mode) in shapes.items():
         if args.ops and name not in args.ops:
             continue
-        copies = max(2, (600 << 20) // (n * k) + 1)  # the fp8 copies alone exceed 2x the Infinity Cache
+        # the copies of the smallest format alone exceed 2x the Infinity Cache (fp8: 1 byte, mxfp4: 17 / 32 per weight)
+        copies = max(2, ((1200 if "mxfp4" in args.formats else 600) << 20) // (n * k) + 1)
         wb = [PackedLinear.random(n, k, DEV) for _ in range(copies)]
-        w8 = [Fp8Linear.from_linear(w) for w in wb]
+        sides = {"bf16": wb}
+        if "fp8" in args.formats:
+            sides["fp8"] = [Fp8Linear.from_linear(w) for w in wb]
+        if "mxfp4" in args.formats:
+            sides["mxfp4"] = [Mxfp4Linear.from_linear(w) for w in wb]
+        if "bf16" not in args.formats:
+            del sides["bf16"]
+        nbytes = {"bf16": 2 * n * k, "fp8": n * k + 4 * n, "mxfp4": n * k // 2 + n * k // 32}
         for m in args.m:
             x = torch.randn(m, k, device=DEV).to(BF16)
             if mode == ops.MODE_QKV:
@@ -66,10 +77,12 @@ def main():
             else:
                 def run(w):
                     ops.linear_swiglu(x, w, rms_eps=1e-5)
-            assert ops._w8_fast(ops.ext(), x, w8[0], mode), "the fp8 side must run the FP8 GEMV"
+            e = ops.ext()
+            assert "fp8" not in sides or ops._w8_fast(e, x, sides["fp8"][0], mode), "the fp8 side must run the FP8 GEMV"
+            assert "mxfp4" not in sides or ops._w4_fast(e, x, sides["mxfp4"][0], mode), "the MXFP4 GEMV must run"
             ops.GEMV_VARIANT = 1  # the bf16 side: the untouched default form (not the tuner's pick)
             graphs = {}
-            for tag, ws in (("bf16", wb), ("fp8", w8)):
+            for tag, ws in sides.items():
                 for i in range(2):
                     run(ws[i])
                 torch.cuda.synchronize()
@@ -80,9 +93,9 @@ def main():
                 graphs[tag] = g
             ops.GEMV_VARIANT = 0
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            times = {"bf16": [], "fp8": []}
+            times = {tag: [] for tag in sides}
             for r in range(args.rounds + 1):
-                for tag in ("bf16", "fp8"):
+                for tag in sides:
                     ev0.record()
                     graphs[tag].replay()
                     ev1.record()
@@ -90,15 +103,18 @@ def main():
                     if r:  # (round 0 warms the graphs)
                         times[tag].append(ev0.elapsed_time(ev1) * 1000.0 / (2 * copies))
             rec = {"op": name, "n": n, "k": k, "m": m, "copies": copies, "rounds": args.rounds}
-            for tag, nbytes in (("bf16", 2 * n * k), ("fp8", n * k + 4 * n)):
+            for tag in sides:
                 t = times[tag]
                 rec[f"{tag}_us_min"] = round(min(t), 2)
                 rec[f"{tag}_us_median"] = round(statistics.median(t), 2)
-                rec[f"{tag}_TBps"] = round(nbytes / min(t) / 1e6, 3)
-            rec["bf16_over_fp8"] = round(rec["bf16_us_median"] / rec["fp8_us_median"], 3)
+                rec[f"{tag}_us_max"] = round(max(t), 2)
+                rec[f"{tag}_TBps"] = round(nbytes[tag] / min(t) / 1e6, 3)
+            for a, b in (("bf16", "fp8"), ("bf16", "mxfp4"), ("fp8", "mxfp4")):
+                if a in sides and b in sides:
+                    rec[f"{a}_over_{b}"] = round(rec[f"{a}_us_median"] / rec[f"{b}_us_median"], 3)
             print(json.dumps(rec), flush=True)
             del graphs
-        del wb, w8
+        del sides, wb
         torch.cuda.empty_cache()
 
 

@@ -24,9 +24,10 @@ def main():
     ap.add_argument("--sample", action="store_true")
     ap.add_argument("--tp-proxy", type=int, default=1, help="> 1: ONE rank of that MP degree on this GPU "
                     "(parallel/comm.py TPRankProxyComm; bench.py tp_rank_proxy)")
-    ap.add_argument("--weights", nargs="+", choices=["bf16", "fp8"], default=["bf16"],
-                    help="fp8: the layer projections quantised to FP8 e4m3 (LLaMAForCausalLM.quantize_weights_); "
-                    "`bf16 fp8`: one model of each in this process, measured alternately per point")
+    ap.add_argument("--weights", nargs="+", choices=["bf16", "fp8", "mxfp4"], default=["bf16"],
+                    help="fp8 / mxfp4: the layer projections quantised to FP8 e4m3 / MXFP4 "
+                    "(LLaMAForCausalLM.quantize_weights_); `bf16 fp8 mxfp4`: one model of each in this process, "
+                    "measured alternately per point")
     ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"],
                     help="KV-cache format (LLaMAForCausalLM.set_kv_cache_format; fp8: e4m3 rows with power-of-two "
                     "scales); `bf16 fp8`: the same model with each, measured alternately per point")
@@ -46,8 +47,8 @@ def main():
     models = {}
     for wf in args.weights:
         models[wf] = LLaMAForCausalLM(cfg, device="cuda", comm=comm, _do_init=False).init_random(seed=1)
-        if wf == "fp8":
-            models[wf].quantize_weights_("fp8_e4m3")
+        if wf != "bf16":
+            models[wf].quantize_weights_("fp8_e4m3" if wf == "fp8" else "mxfp4")
     for b in args.batch:
         for rep in range(args.reps):
             for wf, kv in ((wf, kv) for wf in models for kv in args.kv):
