@@ -59,10 +59,13 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
 
 
 def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int = 256, temperature: float = 0.8,
-         top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16"):
-    """Reference ``main`` (jax_example.py:33-40)."""
+         top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1):
+    """Reference ``main`` (jax_example.py:33-40). ``num_beams > 1``: beam search (temperature is then taken as 0)."""
     generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache)
-    results = generator.generate_from_str(PROMPTS, max_gen_len=max_gen_len, temperature=temperature, top_p=top_p)
+    if num_beams > 1:
+        temperature = 0.0
+    results = generator.generate_from_str(PROMPTS, max_gen_len=max_gen_len, temperature=temperature, top_p=top_p,
+                                          num_beams=num_beams)
     if int(os.environ.get("RANK", "0")) == 0:
         for result in results:
             print(result)
@@ -71,7 +74,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 
 
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
-              weights: str = "bf16", kv_cache: str = "bf16"):
+              weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -85,8 +88,8 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
         model.set_kv_cache_format("fp8_e4m3")
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
                          dtype=torch.int32)
-    gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0,
-                          temperature=temperature, top_p=top_p, pad_token_id=0, eos_token_id=-1)
+    gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0 and num_beams == 1,
+                          temperature=temperature, top_p=top_p, pad_token_id=0, eos_token_id=-1, num_beams=num_beams)
     t0 = time.perf_counter()
     seq = model.generate(toks, generation_config=gc).sequences
     torch.cuda.synchronize() if torch.cuda.is_available() else None
@@ -115,10 +118,14 @@ if __name__ == "__main__":
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: KV caches of FP8 e4m3 rows (one power-of-two scale per row, kv head and slot): 132 bytes "
                     "per 128-value row instead of 256")
+    ap.add_argument("--num_beams", type=int, default=1,
+                    help="> 1: beam search with that many beams (2..8; no sampling, no tensor parallelism)")
     a = ap.parse_args()
     if a.synthetic:
-        synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache)
+        synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
+                  a.num_beams)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
-        main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache)
+        main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
+             a.num_beams)

@@ -883,6 +883,77 @@ void decode_update(Tensor nxt, Tensor finished, Tensor sequences, Tensor cur_len
      "decode_update");
 }
 
+// ---- beam search (beam.hip) ----
+void check_beam_state(const Tensor& running_score, const Tensor& score, const Tensor& is_finished, const Tensor& inv_pen,
+                      const Tensor& cur_len, const Tensor& alive, int64_t& b, int64_t& k, int64_t L, int64_t S) {
+  for (auto* t : {&running_score, &score, &is_finished, &inv_pen, &cur_len, &alive}) check_gpu(*t, "beam state");
+  check(running_score.scalar_type() == torch::kFloat32 && score.scalar_type() == torch::kFloat32 &&
+            inv_pen.scalar_type() == torch::kFloat32 && is_finished.scalar_type() == torch::kInt32 &&
+            cur_len.scalar_type() == torch::kInt32 && alive.scalar_type() == torch::kInt32,
+        "beam state dtypes");
+  check(running_score.dim() == 2, "beam: running_score [B, K]");
+  b = running_score.size(0);
+  k = running_score.size(1);
+  check(b >= 1 && k >= 2 && k <= 8, "beam: B >= 1, 2 <= K <= 8");
+  check(score.numel() == b * k && is_finished.numel() == b * k && cur_len.numel() == 1 && alive.numel() == 1,
+        "beam state shapes");
+  check(S >= 1 && S <= L && L < (1 << 30) && inv_pen.numel() == L + 1, "beam: 1 <= S <= L, inv_pen [L + 1]");
+}
+
+void beam_alive(Tensor running_score, Tensor score, Tensor is_finished, Tensor inv_pen, Tensor cur_len, Tensor alive,
+                int64_t L, int64_t S, int64_t early, bool never_full) {
+  int64_t b, k;
+  check_beam_state(running_score, score, is_finished, inv_pen, cur_len, alive, b, k, L, S);
+  check(early >= 0 && early <= 2, "beam: early_stopping code 0 / 1 / 2");
+  rc(jla::beam_alive(ptr<float>(running_score), ptr<float>(score), ptr<int32_t>(is_finished), ptr<float>(inv_pen),
+                     ptr<int32_t>(cur_len), ptr<int32_t>(alive), b, k, L, S, early, never_full ? 1 : 0, stream()),
+     "beam_alive");
+}
+
+void beam_step(Tensor cand_v, Tensor cand_i, Tensor lse, Tensor running_seq, Tensor seq, Tensor running_score,
+               Tensor score, Tensor is_finished, Tensor inv_pen, Tensor cur_len, Tensor slot, Tensor tokens,
+               Tensor positions, Tensor alive, Tensor beam_idx, int64_t S, int64_t eos, int64_t early) {
+  check(running_seq.dim() == 3, "beam_step: running_seq [B, K, L]");
+  const int64_t L = running_seq.size(2);
+  int64_t b, k;
+  check_beam_state(running_score, score, is_finished, inv_pen, cur_len, alive, b, k, L, S);
+  for (auto* t : {&cand_v, &cand_i, &lse, &running_seq, &seq, &slot, &tokens, &positions, &beam_idx})
+    check_gpu(*t, "beam_step arg");
+  check(cand_v.scalar_type() == torch::kFloat32 && lse.scalar_type() == torch::kFloat32, "beam_step: fp32 candidates");
+  for (auto* t : {&cand_i, &running_seq, &seq, &slot, &tokens, &positions, &beam_idx})
+    check(t->scalar_type() == torch::kInt32, "beam_step: int32 tensors");
+  check(running_seq.size(0) == b && running_seq.size(1) == k && seq.sizes() == running_seq.sizes(),
+        "beam_step: running_seq / seq [B, K, L]");
+  check(cand_v.numel() == b * k * 2 * k && cand_i.numel() == b * k * 2 * k && lse.numel() == b * k,
+        "beam_step: candidates [B*K, 2K], lse [B*K]");
+  check(tokens.numel() == b * k && positions.numel() == b * k && beam_idx.numel() == b * k && slot.numel() == 1,
+        "beam_step: tokens / positions / beam_idx [B*K], slot [1]");
+  check(early >= 0 && early <= 2, "beam: early_stopping code 0 / 1 / 2");
+  rc(jla::beam_step(ptr<float>(cand_v), ptr<int32_t>(cand_i), ptr<float>(lse), ptr<int32_t>(running_seq),
+                    ptr<int32_t>(seq), ptr<float>(running_score), ptr<float>(score), ptr<int32_t>(is_finished),
+                    ptr<float>(inv_pen), ptr<int32_t>(cur_len), ptr<int32_t>(slot), ptr<int32_t>(tokens),
+                    ptr<int32_t>(positions), ptr<int32_t>(alive), ptr<int32_t>(beam_idx), b, k, L, S, eos, early,
+                    stream()),
+     "beam_step");
+}
+
+// t: one cache tensor [layers, B*K, heads, T] or [layers, B*K, heads, T, Dh], any 1-, 2- or 4-byte element type
+void kv_beam_reorder(Tensor t, Tensor beam_idx, Tensor slot, int64_t k) {
+  check_gpu(t, "kv_beam_reorder cache");
+  check_gpu(beam_idx, "beam_idx");
+  check_gpu(slot, "slot");
+  check(beam_idx.scalar_type() == torch::kInt32 && slot.scalar_type() == torch::kInt32 && slot.numel() == 1,
+        "kv_beam_reorder: int32 beam_idx, slot [1]");
+  check(t.dim() == 4 || t.dim() == 5, "kv_beam_reorder: cache [layers, rows, heads, T(, Dh)]");
+  check(k >= 2 && k <= 8 && t.size(1) % k == 0 && beam_idx.numel() == t.size(1), "kv_beam_reorder: rows = B * K");
+  const int64_t rb = (t.dim() == 5 ? t.size(4) : 1) * t.element_size();
+  check(rb % 4 == 0 && rb < (1 << 20) && t.size(3) < (1 << 30), "kv_beam_reorder: bytes per slot a multiple of 4");
+  const int r = jla::kv_beam_reorder(t.data_ptr(), ptr<int32_t>(beam_idx), ptr<int32_t>(slot), t.size(0),
+                                     t.size(1) / k, k, t.size(2), t.size(3), rb, stream());
+  check(r != -2, "kv_beam_reorder: layers * groups and heads must each be <= 65535");
+  rc(r, "kv_beam_reorder");
+}
+
 // ---- custom all-reduce (allreduce.hip) -------------------------------------------------------
 py::tuple car_alloc(int64_t max_bytes, int64_t world) {
   void* buf = nullptr;
@@ -1183,7 +1254,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     const int r = reset ? 1 : 0;
     return (int64_t)(jla::jla_bounds_norm_embed(r) | jla::jla_bounds_rope_kv(r) | jla::jla_bounds_sample(r) |
                      jla::jla_bounds_gemm(r) | jla::jla_bounds_gemv(r) | jla::jla_bounds_kv8(r) |
-                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_prefill(r));
+                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r));
   }, "OR of the bounds-checked debug build's error words (JLA_BOUNDS_* bits); always 0 in a release build",
         py::arg("reset") = false);
 #ifdef JLA_DEBUG_BOUNDS
@@ -1299,4 +1370,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
         py::arg("out_v") = py::none(), py::arg("out_i") = py::none(), py::arg("nxt") = py::none(),
         py::arg("temperature") = 1.0, py::arg("top_p") = 1.0, py::arg("seed") = 0, py::arg("step") = py::none());
   m.def("decode_update", &decode_update);
+  m.def("beam_alive", &beam_alive);
+  m.def("beam_step", &beam_step);
+  m.def("kv_beam_reorder", &kv_beam_reorder);
 }

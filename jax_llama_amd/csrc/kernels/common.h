@@ -31,6 +31,7 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 #define JLA_BOUNDS_SEQ 2        // decode step past the sequence buffer
 #define JLA_BOUNDS_ATTN_T 3     // attention asked for keys past the cache (slot >= T)
 #define JLA_BOUNDS_ROPE_POS 4   // position outside the RoPE table
+#define JLA_BOUNDS_BEAM 5       // beam_idx outside [0, num_beams)
 #ifdef JLA_DEBUG_BOUNDS
 static __device__ unsigned int g_jla_bounds_err;
 #define JLA_FLAG(code) atomicOr(&g_jla_bounds_err, 1u << (code))

@@ -227,6 +227,19 @@ int car_set_grid(void* state, int grid);  // collective blocks per launch (0: th
 void car_destroy(void* state);
 int decode_update(const int32_t* nxt, int32_t* finished, int32_t* sequences, int32_t* cur_len, int32_t* tokens,
                   int32_t* positions, int32_t* slot, int B, int L, int pad, int eos, hipStream_t s);
+// beam search (beam.hip): the loop condition into alive[0]; one step of B items x K beams (alive[0] == 0: identity
+// beam_idx, nothing else changes); every beam's cache rows follow its parent (one cache tensor [layers, groups * K,
+// heads, T, RB bytes], slots below slot[0])
+unsigned jla_bounds_beam(int reset);
+int beam_alive(const float* running_score, const float* score, const int32_t* is_finished, const float* inv_pen,
+               const int32_t* cur_len, int32_t* alive, int B, int K, int L, int S, int early, int never_full,
+               hipStream_t s);
+int beam_step(const float* cand_v, const int32_t* cand_i, const float* lse, int32_t* running_seq, int32_t* seq,
+              float* running_score, float* score, int32_t* is_finished, const float* inv_pen, int32_t* cur_len,
+              int32_t* slot, int32_t* tokens, int32_t* positions, const int32_t* alive, int32_t* beam_idx, int B,
+              int K, int L, int S, int eos, int early, hipStream_t s);
+int kv_beam_reorder(void* base, const int32_t* beam_idx, const int32_t* slot, int layers, int groups, int K,
+                    int heads, int T, int RB, hipStream_t s);
 // CU placement (placement.hip): CU-masked streams and a census of where a launch's workgroups run
 int cu_census(uint32_t* out, int blocks, hipStream_t s);
 int cu_mask_stream_create(const uint32_t* mask, int words, hipStream_t* out);

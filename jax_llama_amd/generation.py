@@ -30,14 +30,21 @@ class LLaMA:
         self.mesh = mesh
 
     def generate(self, tokens, attention_mask, max_gen_len: int, temperature: float = 0.8,
-                 top_p: float = 0.95, seed: int = 0) -> torch.Tensor:
+                 top_p: float = 0.95, seed: int = 0, num_beams: int = 1, length_penalty: float = 1.0,
+                 early_stopping=False) -> torch.Tensor:
+        """``num_beams > 1``: beam search (``runtime/engine.py`` BeamEngine); it does not sample, so ``temperature``
+        must then be 0. Returns each prompt's best hypothesis."""
+        if num_beams != 1 and temperature != 0.0:
+            raise ValueError("beam search does not sample: num_beams > 1 needs temperature=0")
         tokens = torch.as_tensor(tokens, dtype=torch.int32) if not torch.is_tensor(tokens) else tokens
         attention_mask = (torch.as_tensor(attention_mask, dtype=torch.int32)
                           if not torch.is_tensor(attention_mask) else attention_mask)
         tokens = with_named_sharding_constraint(tokens, self.mesh, P("dp", None))
         attention_mask = with_named_sharding_constraint(attention_mask, self.mesh, P("dp", None))
         gc = GenerationConfig(
-            num_beams=1,
+            num_beams=num_beams,
+            length_penalty=length_penalty,
+            early_stopping=early_stopping,
             do_sample=temperature != 0.0,
             max_length=max_gen_len + tokens.shape[1],
             pad_token_id=self.tokenizer.eos_id,
@@ -83,7 +90,8 @@ class LLaMA:
         return res
 
     def generate_from_str(self, prompts: List[str], max_gen_len: int, temperature: float = 0.8,
-                          top_p: float = 0.95, seed: int = 0) -> List[str]:
+                          top_p: float = 0.95, seed: int = 0, num_beams: int = 1, length_penalty: float = 1.0,
+                          early_stopping=False) -> List[str]:
         tok = self.tokenizer
         prompt_tokens = [tok.encode(x, bos=True, eos=False) for x in prompts]
         max_prompt = max(len(t) for t in prompt_tokens)
@@ -91,7 +99,8 @@ class LLaMA:
         for i, t in enumerate(prompt_tokens):
             tokens[i, max_prompt - len(t):] = torch.tensor(t, dtype=torch.int32)  # left pad
         attention_mask = (tokens != tok.eos_id).to(torch.int32)
-        out_tokens = self.generate(tokens, attention_mask, max_gen_len, temperature, top_p, seed)
+        out_tokens = self.generate(tokens, attention_mask, max_gen_len, temperature, top_p, seed, num_beams,
+                                   length_penalty, early_stopping)
         # rows of this dp replica only when the outputs could not be gathered (no process group)
         row0 = 0 if out_tokens.shape[0] == len(prompts) else self.mesh.dp_rank * out_tokens.shape[0]
         decoded = []

@@ -161,7 +161,7 @@ def rmsnorm(x: torch.Tensor, weight: torch.Tensor, eps: float) -> torch.Tensor:
 # bounds-checked debug build (JLA_DEBUG_BOUNDS=1 + python build.py --debug-bounds)
 BOUNDS_CODES = {0: "token id outside the vocabulary", 1: "KV-cache write past the cache (slot >= T)",
                 2: "decode step past the sequence buffer", 3: "attention asked for keys past the cache",
-                4: "position outside the RoPE table"}
+                4: "position outside the RoPE table", 5: "beam_idx outside [0, num_beams)"}
 
 
 class BoundsError(RuntimeError):
@@ -985,3 +985,71 @@ def topk_sample(logits: torch.Tensor, k: int, temperature: float, top_p: float, 
     e.topk_merge(cv, ci, k, 1, nxt=nxt, temperature=float(temperature),
                  top_p=1.0 if top_p is None else float(top_p), seed=int(seed) & ((1 << 63) - 1), step=step)
     return nxt
+
+
+# ---------------------------------------------------------------------------------- beam search
+BEAM_MAX = ref.BEAM_MAX
+
+
+def row_lse(logits: torch.Tensor) -> torch.Tensor:
+    """fp32 ``[M]``: log-sum-exp of each row of fp32 logits ``[M, V]`` (``logprob``'s ``mx + log(se)``)."""
+    m = logits.shape[0]
+    _, mx, se = logprob(logits, torch.zeros(m, dtype=torch.int32, device=logits.device))
+    return mx + torch.log(se)
+
+
+def beam_alive(running_score, score, is_finished, inv_pen, cur_len, alive, max_length: int, prompt_len: int,
+               early_stopping, length_penalty: float) -> None:
+    """``alive[0]`` (int32) = beam search's loop condition before the step at ``cur_len`` (``ref.beam_continue``)."""
+    if not _is_gpu(running_score):
+        alive.fill_(int(ref.beam_continue(running_score, score, is_finished, inv_pen, int(cur_len.item()),
+                                          prompt_len, max_length, early_stopping, length_penalty)))
+        return
+    ext().beam_alive(running_score, score, is_finished, inv_pen, cur_len, alive, int(max_length), int(prompt_len),
+                     ref.beam_early_code(early_stopping), early_stopping == "never" and length_penalty > 0.0)
+
+
+def beam_step(cand_v, cand_i, lse, running_seq, seq, running_score, score, is_finished, inv_pen, cur_len, slot,
+              tokens, positions, alive, beam_idx, prompt_len: int, eos: int, early_stopping) -> None:
+    """One beam-search step, in place on the state (``ref.beam_step`` is the definition): ``running_seq`` / ``seq``
+    int32 ``[B, K, L]``, ``running_score`` / ``score`` fp32 ``[B, K]``, ``is_finished`` int32 ``[B, K]``; writes
+    ``beam_idx`` int32 ``[B*K]`` (each beam's parent), the next input ``tokens``, ``positions + 1``, ``cur_len + 1``
+    and ``slot + 1`` (all device words). With ``alive[0] == 0`` it writes the identity ``beam_idx`` and nothing else."""
+    b, k, _ = running_seq.shape
+    if not _is_gpu(running_seq):
+        if not int(alive.item()):
+            beam_idx.copy_(torch.arange(k, dtype=torch.int32).repeat(b).view_as(beam_idx))
+            return
+        out = ref.beam_step(cand_v, cand_i, lse, running_seq, seq, running_score, score, is_finished.bool(), inv_pen,
+                            int(cur_len.item()), prompt_len, eos, early_stopping)
+        for dst, src in zip((running_seq, seq, running_score, score), out[:4]):
+            dst.copy_(src)
+        is_finished.copy_(out[4].to(torch.int32))
+        beam_idx.copy_(out[5].reshape(beam_idx.shape))
+        tokens.copy_(out[6].reshape(tokens.shape))
+        positions.add_(1)
+        cur_len.add_(1)
+        slot.add_(1)
+        return
+    ext().beam_step(cand_v, cand_i, lse, running_seq, seq, running_score, score, is_finished, inv_pen, cur_len, slot,
+                    tokens, positions, alive, beam_idx, int(prompt_len), int(eos), ref.beam_early_code(early_stopping))
+
+
+def kv_beam_tensors(cache):
+    """The tensors of a KVCache that hold per-row state: K and V, and an FP8 cache's scales."""
+    ts = [cache.k, cache.v]
+    if cache.k_scale is not None:
+        ts += [cache.k_scale, cache.v_scale]
+    return ts
+
+
+def kv_beam_reorder(cache, beam_idx: torch.Tensor, k: int) -> None:
+    """Every beam's cache rows follow its parent, in place: for every layer, K and V (and the scales of an FP8 cache),
+    kv head and slot below the cache's device slot counter, ``row[b*k + j] <- row[b*k + beam_idx[b, j]]``. One launch
+    per tensor (2 for bf16, 4 for FP8); groups whose ``beam_idx`` is the identity are skipped. Slots at or past the
+    counter keep their content or receive the same slot of another beam of their group."""
+    for t in kv_beam_tensors(cache):
+        if not _is_gpu(t):
+            ref.kv_beam_reorder(t, beam_idx, k, int(cache.index_t.item()))
+        else:
+            ext().kv_beam_reorder(t, beam_idx.reshape(-1), cache.index_t, int(k))

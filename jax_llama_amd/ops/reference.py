@@ -577,3 +577,107 @@ def topk_sample(logits: torch.Tensor, k: int, temperature: float, top_p: float, 
     score = np.where(keep, v + g, -np.inf)
     choice = score.argmax(-1)
     return idx[torch.arange(b), torch.from_numpy(choice)].to(torch.int32)
+
+
+# ----------------------------------------------------------------------------------
+# Beam search (HF Flax ``_beam_search`` semantics; the README's "Beam search" section is the definition)
+# ----------------------------------------------------------------------------------
+BEAM_NEG = -1.0e7
+BEAM_MAX = 8  # num_beams <= 8: K x 2K <= 128 candidates per batch item (ranked by counting in the kernel)
+
+
+def beam_early_code(early_stopping) -> int:
+    """``early_stopping`` as the kernels take it: False -> 0, True -> 1, "never" -> 2."""
+    if early_stopping is True:
+        return 1
+    if early_stopping is False:
+        return 0
+    if early_stopping == "never":
+        return 2
+    raise ValueError(f"early_stopping must be True, False or 'never', got {early_stopping!r}")
+
+
+def beam_inv_pen(max_length: int, length_penalty: float) -> torch.Tensor:
+    """fp32 ``[max_length + 1]``: ``1 / t ** length_penalty`` computed in fp64 and rounded once (entry 0 is unused).
+    Every score is multiplied by an entry of this table, so the CPU and the GPU do the same IEEE multiply; HF
+    divides by the power instead, which differs by at most one rounding."""
+    import numpy as np
+    t = np.arange(max_length + 1, dtype=np.float64)
+    t[0] = 1.0
+    return torch.from_numpy((1.0 / t ** float(length_penalty)).astype(np.float32))
+
+
+def _order_desc(x: torch.Tensor) -> torch.Tensor:
+    """int64 ``[B, n]``: the columns of each row of ``x`` by value descending, ties to the lower column."""
+    import numpy as np
+    v = x.float().cpu().numpy()
+    idx = np.broadcast_to(np.arange(v.shape[1]), v.shape)
+    return torch.from_numpy(np.lexsort((idx, -v), axis=-1).astype(np.int64))
+
+
+def beam_step(cand_v, cand_i, lse, running_seq, seq, running_score, score, is_finished, inv_pen, cur_len: int,
+              prompt_len: int, eos: int, early_stopping):
+    """One beam-search step at ``cur_len = c`` for B items of K beams. ``cand_v`` / ``cand_i`` ``[B*K, 2K]``: each
+    running beam's sorted top-2K logits and their token ids; ``lse`` fp32 ``[B*K]``; ``running_seq`` / ``seq`` int32
+    ``[B, K, L]``; ``running_score`` / ``score`` fp32 ``[B, K]``; ``is_finished`` bool ``[B, K]``. Returns the next
+    ``(running_seq, seq, running_score, score, is_finished, beam_idx int32 [B, K], tokens int32 [B, K])``; the inputs
+    are left as they are. All arithmetic is fp32, one rounding per add / multiply. The penalty of a finished-pool
+    candidate is ONE addition of -1e7, made where the candidate did not just finish or where every slot of its item
+    was already finished under ``early_stopping=True`` (HF's ``add_penalty`` is the OR of the two)."""
+    b, k, length = running_seq.shape
+    k2, c = 2 * k, int(cur_len)
+    assert prompt_len <= c < length and cand_v.shape == (b * k, k2), (prompt_len, c, length, cand_v.shape)
+    neg = torch.tensor(BEAM_NEG, dtype=torch.float32)
+    lp = running_score.float().unsqueeze(-1) + (cand_v.float().view(b, k, k2) - lse.float().view(b, k, 1))
+    flat = lp.reshape(b, k * k2)
+    order = _order_desc(flat)[:, :k2]
+    top_lp = flat.gather(1, order)
+    parent = order // k2
+    token = cand_i.reshape(b, k * k2).gather(1, order).to(torch.int32)
+    just = token == int(eos)
+    run_lp = torch.where(just, neg + top_lp, top_lp)
+    rorder = _order_desc(run_lp)[:, :k]
+    beam_idx = parent.gather(1, rorder).to(torch.int32)
+    tokens = token.gather(1, rorder)
+    cand_seq = running_seq.gather(1, parent[:, :, None].expand(b, k2, length)).clone()
+    cand_seq[:, :, c] = token
+    new_running_seq = cand_seq.gather(1, rorder[:, :, None].expand(b, k, length))
+    new_running_score = run_lp.gather(1, rorder)
+    fin_lp = top_lp * inv_pen[c + 1 - prompt_len]
+    all_fin = is_finished.bool().all(1, keepdim=True) & (early_stopping is True)
+    fin_lp = torch.where(~just | all_fin, fin_lp + neg, fin_lp)
+    m_score = torch.cat([score.float(), fin_lp], 1)
+    m_seq = torch.cat([seq, cand_seq], 1)
+    m_fin = torch.cat([is_finished.bool(), just], 1)
+    forder = _order_desc(m_score)[:, :k]
+    return (new_running_seq, m_seq.gather(1, forder[:, :, None].expand(b, k, length)), new_running_score,
+            m_score.gather(1, forder), m_fin.gather(1, forder), beam_idx, tokens)
+
+
+def beam_continue(running_score, score, is_finished, inv_pen, cur_len: int, prompt_len: int, max_length: int,
+                  early_stopping, length_penalty: float) -> bool:
+    """The loop condition, evaluated before the step at ``cur_len`` and global over the batch."""
+    c = int(cur_len)
+    fin = is_finished.bool()
+    if c >= max_length:
+        return False
+    if early_stopping is True and bool(fin.all()):
+        return False
+    if c == prompt_len:  # the first step always runs
+        return True
+    d = max_length - prompt_len if (early_stopping == "never" and length_penalty > 0.0) else c - prompt_len
+    best_running = running_score.float()[:, 0] * inv_pen[d]
+    neg = torch.tensor(BEAM_NEG, dtype=torch.float32)
+    worst_finished = torch.where(fin.any(1), score.float().min(1).values, neg)
+    return bool((best_running > worst_finished).any())
+
+
+def kv_beam_reorder(t: torch.Tensor, beam_idx: torch.Tensor, k: int, count: int) -> torch.Tensor:
+    """In place on one cache tensor ``[L, B*K, Hkv, T, ...]`` (values or scales): slots ``[0, count)`` of row
+    ``b*K + j`` become those of row ``b*K + beam_idx[b, j]``; later slots keep their content."""
+    rows = t.shape[1]
+    b = rows // k
+    src = (torch.arange(b, device=t.device)[:, None] * k + beam_idx.reshape(b, k).long().to(t.device)).reshape(-1)
+    n = max(0, min(int(count), t.shape[3]))
+    t[:, :, :, :n] = t.index_select(1, src)[:, :, :, :n]
+    return t

@@ -20,6 +20,8 @@ MI355X execution model (replaces XLA's compiled ``lax.while_loop``):
     work besides the launch;
   * the host polls the finished flags only every ``check_every`` steps (rows that finished
     earlier keep emitting ``pad``, so polling late never changes the output).
+
+``num_beams > 1``: HF Flax ``_beam_search`` on a ``BeamEngine`` (below), the same execution model over ``B * K`` rows.
 """
 from __future__ import annotations
 
@@ -52,6 +54,10 @@ class GenerationConfig:
     pad_token_id: Optional[int] = None
     eos_token_id: Optional[int] = None
     seed: int = 0
+    # beam search (num_beams > 1; BeamEngine)
+    length_penalty: float = 1.0
+    early_stopping: object = False  # False, True or "never"
+    num_return_sequences: int = 1
 
 
 # prompt tokens per prefill forward (DecodeEngine._prefill_rows): larger batches run their prefill in row chunks
@@ -68,6 +74,7 @@ def _fused_greedy() -> bool:
 @dataclass
 class GenerateOutput:
     sequences: torch.Tensor
+    scores: Optional[torch.Tensor] = None  # beam search: fp32 [B * num_return_sequences], the hypotheses' scores
 
 
 # --------------------------------------------------------------------------------------
@@ -348,6 +355,141 @@ class DecodeEngine:
         return self.sequences
 
 
+class BeamEngine(DecodeEngine):
+    """Beam search (``num_beams = K > 1``) over ``B * K`` cache rows, row ``b*K + j`` = beam j of prompt b. The
+    definition is HF Flax ``_beam_search`` as written out in the README's "Beam search" section and in
+    ``ops/reference.py`` (``beam_step`` / ``beam_continue``); scores are multiplied by ``1 / t ** length_penalty``
+    (one fp32 table, ``ref.beam_inv_pen``) where HF divides by the power: at most one rounding apart.
+
+    All beams of a search have the same length, so the one device slot counter stays. A decode step is the forward,
+    ``topk_candidates(2K)``, the rows' log-sum-exp, ``beam_alive`` + ``beam_step`` (the selection and the whole state
+    update, on the device) and ``kv_beam_reorder`` (every beam's cache rows follow its parent): fixed-shape, captured
+    once and replayed. Once the loop condition fails (``alive == 0``) a replayed step changes nothing, so the host
+    polls ``alive`` only every ``check_every`` steps."""
+
+    def __init__(self, model, batch_size: int, num_beams: int, max_length: int, use_graph: Optional[bool] = None,
+                 check_every: int = 16):
+        if model.comm.size > 1:
+            raise NotImplementedError("beam search under tensor parallelism (vocab-parallel logits) is not supported")
+        if not 2 <= num_beams <= ops.BEAM_MAX:
+            raise ValueError(f"num_beams must be in [2, {ops.BEAM_MAX}], got {num_beams}")
+        super().__init__(model, batch_size * num_beams, max_length, use_graph, check_every)
+        self.nb, self.k = batch_size, num_beams
+        dev = self.device
+        self.running_seq = self.sequences.view(batch_size, num_beams, max_length)
+        self.seq = torch.zeros_like(self.running_seq)
+        self.running_score = torch.zeros(batch_size, num_beams, dtype=torch.float32, device=dev)
+        self.score = torch.zeros_like(self.running_score)
+        self.is_finished = self.finished.view(batch_size, num_beams)
+        self.alive = torch.ones(1, dtype=torch.int32, device=dev)
+        self.beam_idx = torch.zeros(batch_size * num_beams, dtype=torch.int32, device=dev)
+        self.inv_pen = torch.ones(max_length + 1, dtype=torch.float32, device=dev)
+        self.prompt_len = 0
+        self.reorder = ops.kv_beam_reorder  # (cache, beam_idx, K), in place
+        self.beam_idx_log: Optional[list] = None  # eager runs: a list here receives every step's beam_idx (CPU copy)
+
+    def _beam_select(self, logits: torch.Tensor):
+        gc, k = self.gc, self.k
+        logits = logits.float().contiguous()
+        cand_v, cand_i = ops.topk_candidates(logits, 2 * k)
+        lse = ops.row_lse(logits)
+        ops.beam_alive(self.running_score, self.score, self.is_finished, self.inv_pen, self.cur_len, self.alive,
+                       self.max_length, self.prompt_len, gc.early_stopping, float(gc.length_penalty))
+        ops.beam_step(cand_v.contiguous(), cand_i.to(torch.int32).contiguous(), lse, self.running_seq, self.seq,
+                      self.running_score, self.score, self.is_finished, self.inv_pen, self.cur_len, self.cache.index_t,
+                      self.tokens, self.positions, self.alive, self.beam_idx, self.prompt_len,
+                      int(gc.eos_token_id), gc.early_stopping)
+        self.reorder(self.cache, self.beam_idx, k)
+        if self.beam_idx_log is not None and not self.use_graph:
+            self.beam_idx_log.append(self.beam_idx.cpu().clone())
+
+    def _decode_step(self):
+        logits, *_ = self.model.forward_tokens(self.tokens, self.positions, self.cache, self.cache.index_t,
+                                               self.kv_start, self.key_mask, logits_mode="last")
+        self._beam_select(logits)
+
+    def prefill(self, input_ids: torch.Tensor, attention_mask: Optional[torch.Tensor]):
+        """The B prompts run once into a temporary B-row cache of length S, which is then broadcast into the ``B*K``-row
+        cache; the first beam step runs on the prefill logits replicated K times (the ``[0, -1e7, ...]`` initial
+        running scores make that equal to a K-fold prefill)."""
+        from ..models.llama import mask_to_kv_start
+        model, dev, gc, k = self.model, self.device, self.gc, self.k
+        ids = input_ids.to(dev, torch.int32)
+        b, s = ids.shape
+        assert b == self.nb and s < self.max_length
+        if 2 * k > model.vocab_local:
+            raise ValueError(f"num_beams {k} needs a vocabulary of at least {2 * k} entries")
+        mask = torch.ones(b, s, dtype=torch.int32) if attention_mask is None else attention_mask.to("cpu", torch.int32)
+        pos_dev = (mask.cumsum(-1) - 1).to(torch.int32).to(dev)
+        # the prompts, once
+        tmp = model.init_cache(b, s)
+        kv_start_b, key_mask_b = mask_to_kv_start(mask, dev)
+        rows = max(1, PREFILL_TOKENS // max(1, s))
+        parts = []
+        for b0 in range(0, b, rows):
+            b1 = min(b, b0 + rows)
+            km = key_mask_b[b0:b1] if key_mask_b is not None else None
+            lg, *_ = model.forward_tokens(ids[b0:b1], pos_dev[b0:b1], tmp.rows(b0, b1), 0, kv_start_b[b0:b1], km,
+                                          logits_mode="last")
+            parts.append(lg)
+        logits = parts[0] if len(parts) == 1 else torch.cat(parts)
+        # ... broadcast to the K beams of each prompt
+        self.cache.reset()
+        for dst, src in zip(ops.kv_beam_tensors(self.cache), ops.kv_beam_tensors(tmp)):
+            dst.unflatten(1, (b, k))[:, :, :, :, :s].copy_(src.unsqueeze(2))
+        del tmp
+        self.cache.advance(s)
+        ext_mask = torch.ones(b, self.max_length, dtype=torch.int32)
+        ext_mask[:, :s] = mask
+        kv_start, key_mask = mask_to_kv_start(ext_mask.repeat_interleave(k, 0), dev)
+        self.kv_start.copy_(kv_start)
+        if key_mask is not None:
+            if self._key_mask_buf is None:
+                self._key_mask_buf = torch.empty_like(key_mask)
+            self._key_mask_buf.copy_(key_mask)
+            key_mask = self._key_mask_buf
+        self.key_mask = key_mask
+        # the search state
+        self.prompt_len = s
+        self.inv_pen.copy_(ref.beam_inv_pen(self.max_length, float(gc.length_penalty)))
+        self.running_seq.fill_(gc.pad_token_id)
+        self.running_seq[:, :, :s] = ids[:, None]
+        self.seq.copy_(self.running_seq)
+        self.running_score.fill_(ref.BEAM_NEG)
+        self.running_score[:, 0] = 0.0
+        self.score.fill_(ref.BEAM_NEG)
+        self.is_finished.zero_()
+        self.alive.fill_(1)
+        self.cur_len.fill_(s)
+        self.positions.copy_(pos_dev[:, -1:].repeat_interleave(k, 0))
+        # beam_step advances the slot; the prefill already counted the S prompt slots
+        self.cache.index_t.sub_(1)
+        self._beam_select(logits.repeat_interleave(k, 0))
+        self.cache.index = s
+        return s + 1
+
+    def _graph_state(self):
+        # by-value launch arguments of the captured step: K, S, eos, early_stopping and whether length_penalty > 0 with
+        # "never" (beam_alive); pad and length_penalty are listed although the step reads them from device buffers
+        gc = self.gc
+        return (self.k, self.prompt_len, float(gc.length_penalty), gc.early_stopping, int(gc.pad_token_id),
+                int(gc.eos_token_id), self.cache.kv_format, self.key_mask is not None, ops.workspace.generation,
+                ops.QKV_ATTN, self.model.comm.reduce_dtype)
+
+    def _poll(self) -> bool:
+        done = not bool(self.alive.item())  # the last step found the loop condition false and changed nothing
+        self._check()
+        return done
+
+    def _run(self, input_ids, attention_mask):
+        super()._run(input_ids, attention_mask)
+        any_fin = self.is_finished.bool().any(1)
+        seqs = torch.where(any_fin[:, None, None], self.seq, self.running_seq)
+        scores = torch.where(any_fin[:, None], self.score, self.running_score)
+        n = self.gc.num_return_sequences
+        return seqs[:, :n].reshape(-1, self.max_length).clone(), scores[:, :n].reshape(-1).clone()
+
+
 _ENGINES: "OrderedDict" = OrderedDict()
 
 
@@ -370,17 +512,17 @@ def drop_engines(model) -> int:
     return len(keys)
 
 
-def get_engine(model, batch_size: int, max_length: int) -> DecodeEngine:
-    """Per-(model, B, max_length) engines (each owns a KV cache and a captured decode graph), kept in
+def get_engine(model, batch_size: int, max_length: int, num_beams: int = 1) -> DecodeEngine:
+    """Per-(model, B, max_length, num_beams) engines (each owns a KV cache and a captured decode graph), kept in
     LRU order and bounded by the bytes of their KV caches. The model's KV-cache format is part of the key: an engine
-    owns a cache of one format."""
+    owns a cache of one format. ``num_beams > 1``: a BeamEngine over ``B * num_beams`` cache rows."""
     fmt = getattr(model, "kv_cache_format", "bf16")
-    key = (id(model), batch_size, max_length, fmt)
+    key = (id(model), batch_size, max_length, fmt, num_beams)
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)
         return eng
-    need = (model.config.num_hidden_layers * 2 * batch_size * model.n_kv_heads * max_length *
+    need = (model.config.num_hidden_layers * 2 * batch_size * num_beams * model.n_kv_heads * max_length *
             kv_row_bytes(fmt, model.head_dim))
     budget = _engine_budget(model)
     held = sum(e.cache.nbytes() for e in _ENGINES.values())
@@ -388,7 +530,8 @@ def get_engine(model, batch_size: int, max_length: int) -> DecodeEngine:
         _, old = _ENGINES.popitem(last=False)
         held -= old.cache.nbytes()
         del old
-    eng = DecodeEngine(model, batch_size, max_length)
+    eng = (DecodeEngine(model, batch_size, max_length) if num_beams == 1
+           else BeamEngine(model, batch_size, num_beams, max_length))
     _ENGINES[key] = eng
     return eng
 
@@ -400,8 +543,17 @@ def generate(model, input_ids, attention_mask=None, generation_config: Optional[
     for k, v in kwargs.items():
         if hasattr(gc, k):
             setattr(gc, k, v)
-    if gc.num_beams != 1:
-        raise NotImplementedError("beam search is not used by the reference (num_beams=1)")
+    beams = gc.num_beams != 1
+    if beams:
+        if not isinstance(gc.num_beams, int) or not 2 <= gc.num_beams <= ops.BEAM_MAX:
+            raise ValueError(f"num_beams must be 1 (no beam search) or in [2, {ops.BEAM_MAX}], got {gc.num_beams!r}")
+        if gc.do_sample:
+            raise ValueError("beam search does not sample: num_beams > 1 needs do_sample=False")
+        if not 1 <= gc.num_return_sequences <= gc.num_beams:
+            raise ValueError(f"num_return_sequences must be in [1, num_beams], got {gc.num_return_sequences}")
+        ref.beam_early_code(gc.early_stopping)  # ValueError for anything but True / False / "never"
+        if model.comm.size > 1:
+            raise NotImplementedError("beam search under tensor parallelism (vocab-parallel logits) is not supported")
     ids = input_ids if torch.is_tensor(input_ids) else torch.as_tensor(input_ids)
     b, s = ids.shape
     if gc.max_length is None:
@@ -413,8 +565,15 @@ def generate(model, input_ids, attention_mask=None, generation_config: Optional[
     if prng_key is not None:
         gc.seed = int(prng_key) if not torch.is_tensor(prng_key) else int(prng_key.reshape(-1)[0])
     if s >= gc.max_length:
-        return GenerateOutput(sequences=ids.to(model.device, torch.int32)[:, : gc.max_length])
-    eng = get_engine(model, b, gc.max_length)
-    seq = eng.run(ids, attention_mask if attention_mask is None or torch.is_tensor(attention_mask)
+        out = ids.to(model.device, torch.int32)[:, : gc.max_length]
+        if beams:  # nothing to generate: every hypothesis is its prompt, with score 0
+            n = gc.num_return_sequences
+            return GenerateOutput(sequences=out.repeat_interleave(n, 0),
+                                  scores=torch.zeros(b * n, dtype=torch.float32, device=model.device))
+        return GenerateOutput(sequences=out)
+    eng = get_engine(model, b, gc.max_length, gc.num_beams)
+    res = eng.run(ids, attention_mask if attention_mask is None or torch.is_tensor(attention_mask)
                   else torch.as_tensor(attention_mask), gc)
-    return GenerateOutput(sequences=seq.clone())
+    if beams:
+        return GenerateOutput(sequences=res[0], scores=res[1])
+    return GenerateOutput(sequences=res.clone())
