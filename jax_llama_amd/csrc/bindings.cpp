@@ -883,6 +883,47 @@ void decode_update(Tensor nxt, Tensor finished, Tensor sequences, Tensor cur_len
      "decode_update");
 }
 
+// ---- logits processors (logits_proc.hip) ----
+void process_logits(Tensor logits, Tensor sequences, Tensor cur_len, Tensor hist_start, int64_t col_offset,
+                    int64_t vocab, double p, double inv_p, int64_t n, Tensor suppress, Tensor stop, Tensor min_len) {
+  for (auto* t : {&logits, &sequences, &cur_len, &hist_start, &suppress, &stop, &min_len})
+    check_gpu(*t, "process_logits arg");
+  check(logits.scalar_type() == torch::kFloat32 && logits.dim() == 2, "process_logits: fp32 logits [B, V]");
+  for (auto* t : {&sequences, &cur_len, &hist_start, &suppress, &stop, &min_len})
+    check(t->scalar_type() == torch::kInt32, "process_logits: int32 tensors");
+  const int64_t b = logits.size(0), v = logits.size(1);
+  TORCH_CHECK_VALUE(v <= jla::process_logits_max_v(), "jax_llama_amd._C: process_logits: at most ",
+                    jla::process_logits_max_v(), " logits per row (the LDS bitmap), got ", v);
+  check(v >= 1 && col_offset >= 0 && vocab >= col_offset + v && vocab < (int64_t(1) << 31),
+        "process_logits: 0 <= col_offset, col_offset + V <= vocab < 2^31");
+  check(sequences.dim() == 2 && sequences.size(0) == b && sequences.size(1) >= 1 &&
+            sequences.size(1) < (int64_t(1) << 30) && hist_start.numel() == b && cur_len.numel() == 1,
+        "process_logits: sequences [B, L], hist_start [B], cur_len [1]");
+  check(suppress.numel() == 64 && stop.numel() == 8 && min_len.numel() == 1,
+        "process_logits: suppress [64], stop [8], min_len [1]");
+  check(p > 0 && (float)p > 0.f && n >= 0 && n < (int64_t(1) << 30), "process_logits: p > 0, n >= 0");
+  rc(jla::process_logits(ptr<float>(logits), b, v, ptr<int32_t>(sequences), sequences.size(1), ptr<int32_t>(cur_len),
+                         ptr<int32_t>(hist_start), col_offset, vocab, (float)p, (float)inv_p, n,
+                         ptr<int32_t>(suppress), ptr<int32_t>(stop), ptr<int32_t>(min_len), stream()),
+     "process_logits");
+}
+
+void decode_update_set(Tensor nxt, Tensor finished, Tensor sequences, Tensor cur_len, Tensor tokens, Tensor positions,
+                       Tensor slot, int64_t pad, Tensor stop) {
+  for (auto* t : {&nxt, &finished, &sequences, &cur_len, &tokens, &positions, &slot, &stop}) {
+    check_gpu(*t, "decode_update_set arg");
+    check(t->scalar_type() == torch::kInt32, "decode_update_set: int32 tensors");
+  }
+  const int64_t b = nxt.numel();
+  check(finished.numel() == b && tokens.numel() == b && positions.numel() == b && sequences.dim() == 2 &&
+            sequences.size(0) == b && cur_len.numel() == 1 && slot.numel() == 1 && stop.numel() == 8,
+        "decode_update_set shapes (stop: int32 [8])");
+  rc(jla::decode_update_set(ptr<int32_t>(nxt), ptr<int32_t>(finished), ptr<int32_t>(sequences),
+                            ptr<int32_t>(cur_len), ptr<int32_t>(tokens), ptr<int32_t>(positions), ptr<int32_t>(slot),
+                            b, sequences.size(1), pad, ptr<int32_t>(stop), stream()),
+     "decode_update_set");
+}
+
 // ---- beam search (beam.hip) ----
 void check_beam_state(const Tensor& running_score, const Tensor& score, const Tensor& is_finished, const Tensor& inv_pen,
                       const Tensor& cur_len, const Tensor& alive, int64_t& b, int64_t& k, int64_t L, int64_t S) {
@@ -1254,7 +1295,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     const int r = reset ? 1 : 0;
     return (int64_t)(jla::jla_bounds_norm_embed(r) | jla::jla_bounds_rope_kv(r) | jla::jla_bounds_sample(r) |
                      jla::jla_bounds_gemm(r) | jla::jla_bounds_gemv(r) | jla::jla_bounds_kv8(r) |
-                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r));
+                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r) |
+                     jla::jla_bounds_logits_proc(r));
   }, "OR of the bounds-checked debug build's error words (JLA_BOUNDS_* bits); always 0 in a release build",
         py::arg("reset") = false);
 #ifdef JLA_DEBUG_BOUNDS
@@ -1370,6 +1412,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
         py::arg("out_v") = py::none(), py::arg("out_i") = py::none(), py::arg("nxt") = py::none(),
         py::arg("temperature") = 1.0, py::arg("top_p") = 1.0, py::arg("seed") = 0, py::arg("step") = py::none());
   m.def("decode_update", &decode_update);
+  m.def("process_logits", &process_logits);
+  m.def("decode_update_set", &decode_update_set);
+  m.def("process_logits_max_v", []() { return (int64_t)jla::process_logits_max_v(); });
   m.def("beam_alive", &beam_alive);
   m.def("beam_step", &beam_step);
   m.def("kv_beam_reorder", &kv_beam_reorder);

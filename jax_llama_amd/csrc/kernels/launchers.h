@@ -227,6 +227,18 @@ int car_set_grid(void* state, int grid);  // collective blocks per launch (0: th
 void car_destroy(void* state);
 int decode_update(const int32_t* nxt, int32_t* finished, int32_t* sequences, int32_t* cur_len, int32_t* tokens,
                   int32_t* positions, int32_t* slot, int B, int L, int pad, int eos, hipStream_t s);
+// logits processors (logits_proc.hip), in place on fp32 logits [B, V] (V <= process_logits_max_v()): repetition
+// penalty p (inv_p = fp32(1 / p)), no-repeat n-gram size n (0: off), suppress int32[64] and stop int32[8] (unused
+// entries -1; the stop ids are banned while cur_len[0] < min_len[0]) over the history sequences[b, hist_start[b] :
+// cur_len[0]]; vocab = the whole vocabulary, of which this rank holds columns [col_offset, col_offset + V).
+// decode_update_set: decode_update with a device stop set int32[8]
+unsigned jla_bounds_logits_proc(int reset);
+int process_logits_max_v();
+int process_logits(float* logits, int B, int V, const int32_t* sequences, int L, const int32_t* cur_len,
+                   const int32_t* hist_start, int col_offset, int vocab, float p, float inv_p, int n,
+                   const int32_t* suppress, const int32_t* stop, const int32_t* min_len, hipStream_t s);
+int decode_update_set(const int32_t* nxt, int32_t* finished, int32_t* sequences, int32_t* cur_len, int32_t* tokens,
+                      int32_t* positions, int32_t* slot, int B, int L, int pad, const int32_t* stop, hipStream_t s);
 // beam search (beam.hip): the loop condition into alive[0]; one step of B items x K beams (alive[0] == 0: identity
 // beam_idx, nothing else changes); every beam's cache rows follow its parent (one cache tensor [layers, groups * K,
 // heads, T, RB bytes], slots below slot[0])

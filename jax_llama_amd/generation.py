@@ -31,9 +31,14 @@ class LLaMA:
 
     def generate(self, tokens, attention_mask, max_gen_len: int, temperature: float = 0.8,
                  top_p: float = 0.95, seed: int = 0, num_beams: int = 1, length_penalty: float = 1.0,
-                 early_stopping=False) -> torch.Tensor:
+                 early_stopping=False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                 min_new_tokens: int = 0, stop_token_ids=None) -> torch.Tensor:
         """``num_beams > 1``: beam search (``runtime/engine.py`` BeamEngine); it does not sample, so ``temperature``
-        must then be 0. Returns each prompt's best hypothesis."""
+        must then be 0. Returns each prompt's best hypothesis.
+
+        ``repetition_penalty`` / ``no_repeat_ngram_size`` / ``min_new_tokens``: the logits processors of the README's
+        "Logits processors" section. ``stop_token_ids`` (1 to 8 ids, e.g. the Llama-3 tokenizer's ``stop_tokens``): a
+        row stops on any of them; without it the stop set is ``tokenizer.eos_id`` alone, as before."""
         if num_beams != 1 and temperature != 0.0:
             raise ValueError("beam search does not sample: num_beams > 1 needs temperature=0")
         tokens = torch.as_tensor(tokens, dtype=torch.int32) if not torch.is_tensor(tokens) else tokens
@@ -48,7 +53,10 @@ class LLaMA:
             do_sample=temperature != 0.0,
             max_length=max_gen_len + tokens.shape[1],
             pad_token_id=self.tokenizer.eos_id,
-            eos_token_id=self.tokenizer.eos_id,
+            eos_token_id=self.tokenizer.eos_id if stop_token_ids is None else sorted(int(t) for t in stop_token_ids),
+            repetition_penalty=repetition_penalty,
+            no_repeat_ngram_size=no_repeat_ngram_size,
+            min_new_tokens=min_new_tokens,
             temperature=temperature,
             top_p=top_p,
             seed=seed,
@@ -91,7 +99,9 @@ class LLaMA:
 
     def generate_from_str(self, prompts: List[str], max_gen_len: int, temperature: float = 0.8,
                           top_p: float = 0.95, seed: int = 0, num_beams: int = 1, length_penalty: float = 1.0,
-                          early_stopping=False) -> List[str]:
+                          early_stopping=False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
+                          min_new_tokens: int = 0, stop_token_ids=None) -> List[str]:
+        """``stop_token_ids``: each completion is cut at the first of any of them (default: at ``eos_id``)."""
         tok = self.tokenizer
         prompt_tokens = [tok.encode(x, bos=True, eos=False) for x in prompts]
         max_prompt = max(len(t) for t in prompt_tokens)
@@ -100,16 +110,19 @@ class LLaMA:
             tokens[i, max_prompt - len(t):] = torch.tensor(t, dtype=torch.int32)  # left pad
         attention_mask = (tokens != tok.eos_id).to(torch.int32)
         out_tokens = self.generate(tokens, attention_mask, max_gen_len, temperature, top_p, seed, num_beams,
-                                   length_penalty, early_stopping)
+                                   length_penalty, early_stopping, repetition_penalty, no_repeat_ngram_size,
+                                   min_new_tokens, stop_token_ids)
+        stops = {tok.eos_id} if stop_token_ids is None else {int(t) for t in stop_token_ids}
         # rows of this dp replica only when the outputs could not be gathered (no process group)
         row0 = 0 if out_tokens.shape[0] == len(prompts) else self.mesh.dp_rank * out_tokens.shape[0]
         decoded = []
         for i, t in enumerate(out_tokens.tolist()):
             t = t[t.index(tok.bos_id):]
             t = t[: len(prompt_tokens[row0 + i]) + max_gen_len]
-            try:
-                t = t[: t.index(tok.eos_id)]
-            except ValueError:
-                pass
+            # a stop list is looked for in the completion only (a chat prompt holds end-of-turn tokens of its own)
+            first = 0 if stop_token_ids is None else len(prompt_tokens[row0 + i])
+            cut = [j for j in range(first, len(t)) if t[j] in stops]
+            if cut:
+                t = t[: cut[0]]
             decoded.append(tok.decode(t))
         return decoded

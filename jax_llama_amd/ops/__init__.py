@@ -1053,3 +1053,43 @@ def kv_beam_reorder(cache, beam_idx: torch.Tensor, k: int) -> None:
             ref.kv_beam_reorder(t, beam_idx, k, int(cache.index_t.item()))
         else:
             ext().kv_beam_reorder(t, beam_idx.reshape(-1), cache.index_t, int(k))
+
+
+# ---------------------------------------------------------------------------------- logits processors
+PROC_MAX_STOP, PROC_MAX_SUPPRESS = ref.PROC_MAX_STOP, ref.PROC_MAX_SUPPRESS
+
+
+def proc_max_v() -> int:
+    """Logits per row and rank the kernel takes: the bits of its LDS bitmap (csrc/kernels/logits_proc.hip)."""
+    return int(ext().process_logits_max_v())
+
+
+def id_buffer(ids, size: int, device) -> torch.Tensor:
+    """int32 ``[size]``: ``ids`` then -1, a value no token equals (the suppress and stop buffers of process_logits)."""
+    ids = [int(i) for i in ids]
+    if len(ids) > size:
+        raise ValueError(f"at most {size} ids, got {len(ids)}")
+    return torch.tensor(ids + [-1] * (size - len(ids)), dtype=torch.int32, device=device)
+
+
+def process_logits(logits: torch.Tensor, sequences: torch.Tensor, cur_len: torch.Tensor, hist_start: torch.Tensor,
+                   col_offset: int, vocab: int, repetition_penalty: float, no_repeat_ngram_size: int,
+                   suppress: torch.Tensor, stop: torch.Tensor, min_len: torch.Tensor) -> torch.Tensor:
+    """The logits processors (``ref.process_logits`` is the definition), in place on this rank's fp32 logits
+    ``[B, V_local]``, one launch (csrc/kernels/logits_proc.hip), hipGraph-capturable: ``cur_len`` int32 [1],
+    ``hist_start`` int32 [B], ``suppress`` int32 [64], ``stop`` int32 [8] (unused entries -1) and ``min_len`` int32 [1]
+    are device buffers read at run time; the penalty and the n-gram size are launch arguments."""
+    if logits.dtype != torch.float32 or logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("process_logits: contiguous fp32 logits [B, V_local]")
+    p, n = float(repetition_penalty), int(no_repeat_ngram_size)
+    if not p > 0.0 or n < 0:
+        raise ValueError(f"process_logits: repetition_penalty > 0 and no_repeat_ngram_size >= 0, got {p}, {n}")
+    if not _is_gpu(logits):
+        cfg = ref.LogitsProcessors(p, n, [t for t in suppress.tolist() if t >= 0], [t for t in stop.tolist() if t >= 0],
+                                   int(min_len.item()), int(vocab))
+        return ref.process_logits(logits, sequences, int(cur_len.item()), hist_start, int(col_offset), cfg)
+    if logits.shape[1] > proc_max_v():
+        raise ValueError(f"process_logits: at most {proc_max_v()} logits per row and rank, got {logits.shape[1]}")
+    ext().process_logits(logits, sequences, cur_len, hist_start, int(col_offset), int(vocab), p, ref.inv_penalty(p), n,
+                         suppress, stop, min_len)
+    return logits

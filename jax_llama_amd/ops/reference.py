@@ -15,7 +15,8 @@ Reference semantics being reproduced (``/root/reference/jax_llama/model.py``):
 from __future__ import annotations
 
 import math
-from typing import Optional
+from dataclasses import dataclass
+from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -681,3 +682,74 @@ def kv_beam_reorder(t: torch.Tensor, beam_idx: torch.Tensor, k: int, count: int)
     n = max(0, min(int(count), t.shape[3]))
     t[:, :, :, :n] = t.index_select(1, src)[:, :, :, :n]
     return t
+
+
+# ----------------------------------------------------------------------------------
+# Logits processors (the README's "Logits processors" section is the definition)
+# ----------------------------------------------------------------------------------
+PROC_MAX_STOP = 8       # stop ids per call (eos_token_id as a list)
+PROC_MAX_SUPPRESS = 64  # always-banned ids per call
+
+
+@dataclass
+class LogitsProcessors:
+    """What ``process_logits`` applies, resolved for one call: ``min_len`` is ``max(min_length, S + min_new_tokens)``
+    (the stop ids are banned while ``cur_len < min_len``), ``vocab`` the whole vocabulary (history tokens outside
+    ``[0, vocab)`` are skipped; None: no upper limit)."""
+
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    suppress_tokens: Sequence[int] = ()
+    stop_ids: Sequence[int] = ()
+    min_len: int = 0
+    vocab: Optional[int] = None
+
+    def active(self) -> bool:
+        return (float(self.repetition_penalty) != 1.0 or self.no_repeat_ngram_size > 0 or len(self.suppress_tokens) > 0
+                or (self.min_len > 0 and len(self.stop_ids) > 0))
+
+
+def inv_penalty(p: float) -> float:
+    """``fp32(1 / p)``, computed in fp64 and rounded once: positive logits are multiplied by it where HF divides by
+    ``p`` (at most one rounding apart), so the CPU and the GPU do the same IEEE multiply."""
+    import numpy as np
+    return float(np.float32(1.0 / float(p)))
+
+
+def process_logits(logits: torch.Tensor, sequences: torch.Tensor, cur_len: int, hist_start: torch.Tensor,
+                   col_offset: int, cfg: LogitsProcessors) -> torch.Tensor:
+    """In place on fp32 ``logits [B, V_local]`` (columns ``[col_offset, col_offset + V_local)`` of the vocabulary), per
+    row b over the history ``H = sequences[b, hist_start[b] : cur_len]``: the repetition penalty (each distinct token
+    of H once: ``l > 0 -> l * fp32(1 / p)``, else ``l * p``), then the masks, which store ``-inf``: the token that
+    would complete a repeated n-gram, the suppressed ids, and the stop ids while ``cur_len < min_len``."""
+    assert logits.dtype == torch.float32 and logits.dim() == 2
+    b, v = logits.shape
+    length = sequences.shape[1]
+    cl = max(0, min(int(cur_len), length))
+    p, n = float(cfg.repetition_penalty), int(cfg.no_repeat_ngram_size)
+    p32 = torch.tensor(p, dtype=torch.float32)
+    inv32 = torch.tensor(inv_penalty(p), dtype=torch.float32)
+    hi = cfg.vocab if cfg.vocab is not None else (1 << 62)
+
+    def local(tok: torch.Tensor) -> torch.Tensor:  # this shard's columns of the in-vocabulary tokens of `tok`
+        tok = tok[(tok >= 0) & (tok < hi)] - col_offset
+        return tok[(tok >= 0) & (tok < v)]
+
+    always = local(torch.as_tensor(list(cfg.suppress_tokens), dtype=torch.int64))
+    stops = local(torch.as_tensor(list(cfg.stop_ids), dtype=torch.int64))
+    for r in range(b):
+        hs = max(0, min(int(hist_start[r]), cl))
+        h = sequences[r, hs:cl].to(torch.int64).cpu()
+        row = logits[r]
+        if p != 1.0 and h.numel():
+            cols = torch.unique(local(h))
+            x = row[cols]
+            row[cols] = torch.where(x > 0, x * inv32, x * p32)
+        if n >= 1 and h.numel() >= n:
+            windows = h.unfold(0, n, 1)  # [len - n + 1, n]
+            match = (windows[:, :n - 1] == h[h.numel() - n + 1:]).all(1)
+            row[local(windows[match, n - 1])] = -math.inf
+        row[always] = -math.inf
+        if int(cur_len) < cfg.min_len:
+            row[stops] = -math.inf
+    return logits

@@ -19,19 +19,21 @@ def synthetic_prompts(vocab: int, batch: int, prompt_len: int, seed: int) -> tor
 
 
 def decode_latency(model, batch: int, prompt_len: int = 128, gen_len: int = 256, steps: Optional[int] = None,
-                   seed: int = 0, barrier=None, do_sample: bool = False) -> Dict[str, float]:
+                   seed: int = 0, barrier=None, do_sample: bool = False,
+                   processors: Optional[dict] = None) -> Dict[str, float]:
     """Prefill ``batch`` prompts into a ``prompt_len + gen_len`` cache (``prefill_ms``: the second, warm prefill; the
     first autotunes), capture the decode step (every layer, lm_head, sampler, state update), prefill again, then time
     ``steps`` replays of it -- by default every step of a ``gen_len``-token generation (``gen_len - 1`` replays after
     the prefill's first token, cache length from ``prompt_len + 1`` up), so attention is weighted as in a real
     generation (``kv_len_mean`` reports the mean cache length the steps covered; reference generation.py:35:
-    max_length = S + max_gen_len). Every rank of a TP group must call this with the same arguments."""
+    max_length = S + max_gen_len). Every rank of a TP group must call this with the same arguments.
+    ``processors``: GenerationConfig's logits-processor fields (repetition_penalty, no_repeat_ngram_size, ...)."""
     steps = gen_len - 1 if steps is None else steps
     assert 1 <= steps <= gen_len - 1, "replays must stay inside the cache"
     max_len = prompt_len + gen_len
     eng = DecodeEngine(model, batch, max_len, use_graph=True)
     gc = GenerationConfig(max_length=max_len, do_sample=do_sample, temperature=0.8, top_p=0.95, top_k=50,
-                          pad_token_id=0, eos_token_id=-1)
+                          pad_token_id=0, eos_token_id=-1, **(processors or {}))
     eng.gc = gc
     prompts = synthetic_prompts(model.config.vocab_size, batch, prompt_len, seed)
     dev = model.device

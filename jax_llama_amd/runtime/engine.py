@@ -9,6 +9,8 @@ inherits (``generation.py:28-41`` builds the ``GenerationConfig``):
   * a finished row emits ``pad``; ``is_sent_finished |= next == eos``;
   * greedy = ``argmax`` (first max); sampling = temperature -> top-k (default 50) -> top-p ->
     categorical;
+  * logits processors (repetition penalty, no-repeat n-gram, suppressed ids, minimum length) run on the logits
+    before either, and ``eos`` may be a set of up to 8 ids (the README's "Logits processors" section);
   * positions: ``cumsum(mask) - 1`` for the prompt, then ``last + 1`` per step
     (``model.py:758, 771``).
 
@@ -52,8 +54,15 @@ class GenerationConfig:
     top_p: float = 1.0
     num_beams: int = 1
     pad_token_id: Optional[int] = None
-    eos_token_id: Optional[int] = None
+    eos_token_id: object = None  # one id, or a list of 1 .. 8 ids (the stop set)
     seed: int = 0
+    # logits processors (the README's "Logits processors" section; ops/reference.py process_logits)
+    repetition_penalty: float = 1.0
+    no_repeat_ngram_size: int = 0
+    min_length: int = 0
+    min_new_tokens: int = 0
+    suppress_tokens: Optional[list] = None
+    bad_words_ids: Optional[list] = None  # single-token entries only: they join suppress_tokens
     # beam search (num_beams > 1; BeamEngine)
     length_penalty: float = 1.0
     early_stopping: object = False  # False, True or "never"
@@ -75,6 +84,60 @@ def _fused_greedy() -> bool:
 class GenerateOutput:
     sequences: torch.Tensor
     scores: Optional[torch.Tensor] = None  # beam search: fp32 [B * num_return_sequences], the hypotheses' scores
+
+
+# --------------------------------------------------------------------------------------
+# Logits processors and stop sets
+# --------------------------------------------------------------------------------------
+def stop_ids(gc: GenerationConfig) -> list:
+    """The stop set of ``gc.eos_token_id`` (one id or a list); an id below 0 stands for "none"."""
+    eos = gc.eos_token_id
+    ids = list(eos) if isinstance(eos, (list, tuple)) else ([] if eos is None else [eos])
+    return [int(t) for t in ids if int(t) >= 0]
+
+
+def suppressed_ids(gc: GenerationConfig) -> list:
+    """``suppress_tokens`` plus the single-token entries of ``bad_words_ids``, without duplicates."""
+    ids = [int(t) for t in (gc.suppress_tokens or [])]
+    for word in gc.bad_words_ids or []:
+        word = [word] if isinstance(word, int) else list(word)
+        if len(word) != 1:
+            raise NotImplementedError("bad_words_ids: only single-token entries are supported")
+        ids.append(int(word[0]))
+    return list(dict.fromkeys(ids))
+
+
+def processors_active(gc: GenerationConfig) -> bool:
+    """Whether a decode step runs ``ops.process_logits`` (a stop list alone does not: it only changes the update)."""
+    return (float(gc.repetition_penalty) != 1.0 or gc.no_repeat_ngram_size > 0 or bool(suppressed_ids(gc))
+            or ((gc.min_length > 0 or gc.min_new_tokens > 0) and bool(stop_ids(gc))))
+
+
+def validate_processors(gc: GenerationConfig, vocab: int) -> None:
+    """ValueError for settings outside the definition (``generate`` and ``DecodeEngine.run`` both call it)."""
+    p = gc.repetition_penalty
+    if isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0:
+        raise ValueError(f"repetition_penalty must be a number > 0, got {p!r}")
+    for name in ("no_repeat_ngram_size", "min_length", "min_new_tokens"):
+        val = getattr(gc, name)
+        if isinstance(val, bool) or not isinstance(val, int) or val < 0:
+            raise ValueError(f"{name} must be an int >= 0, got {val!r}")
+    eos = gc.eos_token_id
+    if isinstance(eos, (list, tuple)):
+        if not 1 <= len(eos) <= ops.PROC_MAX_STOP:
+            raise ValueError(f"eos_token_id: a list of 1 to {ops.PROC_MAX_STOP} ids, got {len(eos)}")
+        bad = [t for t in eos if isinstance(t, bool) or not isinstance(t, int) or not 0 <= t < vocab]
+        if bad:
+            raise ValueError(f"eos_token_id: ids outside the vocabulary [0, {vocab}): {bad}")
+    sup = suppressed_ids(gc)
+    if len(sup) > ops.PROC_MAX_SUPPRESS:
+        raise ValueError(f"suppress_tokens (with bad_words_ids): at most {ops.PROC_MAX_SUPPRESS} ids, got {len(sup)}")
+    bad = [t for t in sup if not 0 <= t < vocab]
+    if bad:
+        raise ValueError(f"suppress_tokens: ids outside the vocabulary [0, {vocab}): {bad}")
+    if gc.num_beams != 1 and (processors_active(gc) or isinstance(eos, (list, tuple)) or gc.min_length > 0
+                              or gc.min_new_tokens > 0):
+        raise ValueError("beam search (num_beams > 1) takes no logits processors and no stop list")
 
 
 # --------------------------------------------------------------------------------------
@@ -162,9 +225,24 @@ class DecodeEngine:
         self.keep_graph = False  # keep the captured graph's topology (runtime/benchmark.py counts its kernel nodes)
         self._gen: Optional[torch.Generator] = None
         self.gc: Optional[GenerationConfig] = None
+        # logits processors and the stop set: what changes from call to call lives in these fixed buffers, which the
+        # captured step reads (filled by prefill; unused id slots hold -1)
+        self.hist_start = torch.zeros(batch_size, **i32)  # first attended prompt column (S: none): history start
+        self.stop_ids = torch.full((ops.PROC_MAX_STOP,), -1, **i32)
+        self.suppress_ids = torch.full((ops.PROC_MAX_SUPPRESS,), -1, **i32)
+        self.min_len = torch.zeros(1, **i32)  # max(min_length, S + min_new_tokens)
+        self._processors = False
+        self._stop_set = False
 
     # ---------------------------------------------------------------------------------
     def _next_token(self, logits_local):
+        if self._processors:  # processors -> temperature -> top-k -> top-p, as in HF
+            comm, gc = self.model.comm, self.gc
+            logits_local = logits_local.float().contiguous()
+            v_local = logits_local.shape[1]
+            ops.process_logits(logits_local, self.sequences, self.cur_len, self.hist_start, comm.rank * v_local,
+                               v_local * comm.size, gc.repetition_penalty, gc.no_repeat_ngram_size,
+                               self.suppress_ids, self.stop_ids, self.min_len)
         if self.gc.do_sample:
             return _sample(self.model, logits_local, self.gc, self._gen, self.cur_len)
         return _greedy(self.model, logits_local)
@@ -173,13 +251,22 @@ class DecodeEngine:
         """Device-side HF loop-body bookkeeping (pad for finished rows, eos tracking,
         sequences write, position/slot/cur_len advance)."""
         if self.device.type == "cuda":
+            if self._stop_set:  # eos_token_id is a list: the ids come from the stop buffer
+                ops.ext().decode_update_set(nxt, self.finished, self.sequences, self.cur_len, self.tokens,
+                                            self.positions, self.cache.index_t, int(self.gc.pad_token_id),
+                                            self.stop_ids)
+                return
             ops.ext().decode_update(nxt, self.finished, self.sequences, self.cur_len, self.tokens,
                                     self.positions, self.cache.index_t, int(self.gc.pad_token_id),
                                     int(self.gc.eos_token_id))
             return
         fin = self.finished.bool()
         nxt = torch.where(fin, torch.full_like(nxt, self.gc.pad_token_id), nxt)
-        self.finished.copy_((fin | (nxt == self.gc.eos_token_id)).to(torch.int32))
+        if self._stop_set:
+            hit = (nxt[:, None] == self.stop_ids[None, :]).any(1)
+        else:
+            hit = nxt == self.gc.eos_token_id
+        self.finished.copy_((fin | hit).to(torch.int32))
         cl = int(self.cur_len.item())
         if cl < self.max_length:
             self.sequences[:, cl] = nxt
@@ -189,7 +276,7 @@ class DecodeEngine:
         self.cur_len.add_(1)
 
     def _logits_mode(self) -> str:
-        return "argmax" if _fused_greedy() and not self.gc.do_sample else "last"
+        return "argmax" if _fused_greedy() and not self.gc.do_sample and not self._processors else "last"
 
     def _decode_step(self):
         logits, *_ = self.model.forward_tokens(self.tokens, self.positions, self.cache, self.cache.index_t,
@@ -222,6 +309,7 @@ class DecodeEngine:
         self.sequences.fill_(self.gc.pad_token_id)
         self.sequences[:, :s] = ids
         self.finished.zero_()
+        self._set_processors(mask, s)
         pos_dev = positions.to(dev)
         logits = self._prefill_rows(ids, pos_dev)
         self.cache.advance(s)
@@ -236,6 +324,21 @@ class DecodeEngine:
         self._update(nxt)
         self.cache.index = s  # host mirror (decode steps track the slot on the device)
         return s + 1
+
+    def _set_processors(self, mask: torch.Tensor, s: int):
+        """This call's processor state, into the buffers the captured step reads: each row's history start (its first
+        attended prompt column: left padding is not history, a later hole is), the stop and suppress ids and the
+        minimum-length word."""
+        gc = self.gc
+        self._processors = processors_active(gc)
+        self._stop_set = isinstance(gc.eos_token_id, (list, tuple))
+        if not (self._processors or self._stop_set):
+            return
+        first = torch.where(mask.bool().any(1), mask.ne(0).to(torch.int32).argmax(1), torch.full((mask.shape[0],), s))
+        self.hist_start.copy_(first.to(torch.int32))
+        self.stop_ids.copy_(ops.id_buffer(stop_ids(gc), ops.PROC_MAX_STOP, "cpu"))
+        self.suppress_ids.copy_(ops.id_buffer(suppressed_ids(gc), ops.PROC_MAX_SUPPRESS, "cpu"))
+        self.min_len.fill_(max(int(gc.min_length), s + int(gc.min_new_tokens)))
 
     def _prefill_rows(self, ids: torch.Tensor, pos_dev: torch.Tensor):
         """The prompt forward, in row chunks of at most PREFILL_TOKENS tokens: every kernel then sees at most the
@@ -269,11 +372,17 @@ class DecodeEngine:
         # mask are this engine's own, fixed ones), the sampling mode, and the scalars its launches take by value:
         # pad and eos (decode_update) and the sampler's settings (topk_merge). A call with other values captures again
         # (so does every new seed of a sampling caller: the seed is a launch argument, not a device word).
+        # With processors or a stop list the key grows by their by-value arguments: the penalty (and with it 1 / p)
+        # and the n-gram size. The ids, the minimum length and the history starts are read from this engine's buffers.
         gc = self.gc
         sampler = (gc.top_k, gc.temperature, gc.top_p, int(gc.seed)) if gc.do_sample else None
-        return (gc.do_sample, self.key_mask is not None, ops.workspace.generation, _fused_greedy(),
-                ops.ARGMAX_FUSED_MIN_M, ops.SKINNY_ARGMAX, ops.QKV_ATTN, self.model.comm.reduce_dtype,
-                int(gc.pad_token_id), int(gc.eos_token_id), sampler)
+        key = (gc.do_sample, self.key_mask is not None, ops.workspace.generation, _fused_greedy(),
+               ops.ARGMAX_FUSED_MIN_M, ops.SKINNY_ARGMAX, ops.QKV_ATTN, self.model.comm.reduce_dtype,
+               int(gc.pad_token_id), None if self._stop_set else int(gc.eos_token_id), sampler)
+        if self._processors or self._stop_set:
+            proc = (float(gc.repetition_penalty), int(gc.no_repeat_ngram_size)) if self._processors else None
+            key += (self._stop_set, proc)
+        return key
 
     def _ensure_graph(self):
         if self._graph is not None and self._graph_key == self._graph_state():
@@ -306,6 +415,7 @@ class DecodeEngine:
         ops.check_bounds()  # bounds-checked debug build only (JLA_DEBUG_BOUNDS=1): out-of-range device indices
 
     def run(self, input_ids, attention_mask, gc: GenerationConfig) -> torch.Tensor:
+        validate_processors(gc, self.model.vocab_local * self.model.comm.size)
         self.gc = gc
         rng_saved = None
         if gc.do_sample:
@@ -562,6 +672,9 @@ def generate(model, input_ids, attention_mask=None, generation_config: Optional[
         gc.pad_token_id = model.config.pad_token_id if model.config.pad_token_id >= 0 else 0
     if gc.eos_token_id is None:
         gc.eos_token_id = model.config.eos_token_id
+    if isinstance(gc.eos_token_id, (list, tuple)):
+        gc.eos_token_id = list(gc.eos_token_id)
+    validate_processors(gc, model.config.vocab_size)
     if prng_key is not None:
         gc.seed = int(prng_key) if not torch.is_tensor(prng_key) else int(prng_key.reshape(-1)[0])
     if s >= gc.max_length:

@@ -32,6 +32,11 @@ def main():
                     help="KV-cache format (LLaMAForCausalLM.set_kv_cache_format; fp8: e4m3 rows with power-of-two "
                     "scales); `bf16 fp8`: the same model with each, measured alternately per point")
     ap.add_argument("--reps", type=int, default=1, help="repeats of every point (alternating over --weights and --kv)")
+    ap.add_argument("--repetition-penalty", type=float, default=1.0)
+    ap.add_argument("--no-repeat-ngram", type=int, default=0)
+    ap.add_argument("--min-new-tokens", type=int, default=0,
+                    help="with any of these three logits-processor settings every point is measured with the "
+                    "processors off and on, alternately (record field `processors`)")
     ap.add_argument("--tune-report", action="store_true", help="print the decode-kernel choices and the graph-timed "
                     "microseconds of every candidate measured (ops/autotune.py)")
     args = ap.parse_args()
@@ -49,12 +54,18 @@ def main():
         models[wf] = LLaMAForCausalLM(cfg, device="cuda", comm=comm, _do_init=False).init_random(seed=1)
         if wf != "bf16":
             models[wf].quantize_weights_("fp8_e4m3" if wf == "fp8" else "mxfp4")
+    procs = [("off", None)]
+    if args.repetition_penalty != 1.0 or args.no_repeat_ngram or args.min_new_tokens:
+        procs.append(("on", dict(repetition_penalty=args.repetition_penalty, no_repeat_ngram_size=args.no_repeat_ngram,
+                                 min_new_tokens=args.min_new_tokens)))
     for b in args.batch:
         for rep in range(args.reps):
-            for wf, kv in ((wf, kv) for wf in models for kv in args.kv):
+            for wf, kv, (pname, proc) in ((wf, kv, pr) for wf in models for kv in args.kv for pr in procs):
                 m = models[wf]
                 m.set_kv_cache_format("fp8_e4m3" if kv == "fp8" else "bf16")
-                r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample)
+                r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample,
+                                   processors=proc)
+                r["processors"] = pname
                 r["model"] = args.model
                 r["mp"] = args.tp_proxy
                 r["weights"] = wf
