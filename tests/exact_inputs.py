@@ -8,6 +8,11 @@ against ``ops/reference.py`` and ``tests/test_exact_gpu.py`` runs the HIP kernel
     vectors of the key's residue class mod 128, so ``out * n`` counts the valid keys of every class;
   * attention needle: +-1 keys and q = 32 * K[j*], so the fp32 softmax is exactly one-hot and the output is the V row
     of the needle bit for bit;
+  * attention ladder: keys that equal a +-1 vector u on their first n_j dims and q = gain * u, so every score is the
+    exact number gain * n_j / sqrt(128) and the scores differ by design (up to 181 nats): the softmax is known in fp64
+    and, with the census V, every output element is a sum of non-negative weights checked to a relative bound -- what
+    the census (all weights equal) and the needle (a single weight) cannot weigh: the rescale of l and O by factors
+    strictly between 0 and 1 as the running maximum moves, the weights of the wave and key-split merges;
   * integer GEMM operands whose every partial sum stays below 2^24 (fp32 accumulation exact in any order), with planted
     bf16 rounding ties, and a RoPE table of quarter turns (every rotated value is +- an input integer).
 """
@@ -160,6 +165,125 @@ NEEDLE_MAX_CROSS = 72
 
 def needle_gap(cross: int) -> float:
     return 32.0 * (DH - cross) / math.sqrt(DH)
+
+
+# ----------------------------------------------------------------------------------
+# attention ladder: exact scores that differ by design
+# ----------------------------------------------------------------------------------
+GAINS = (8.0, -8.0, 1.0, -1.0, 16.0, -16.0, 0.25, -2.0)  # powers of two: q = gain * u is exact in bf16
+LADDER_PROFILES = ("ramp", "steps", "saw", "high")
+U_BF16 = 2.0 ** -8  # bf16's unit roundoff
+# Per element |out - want| <= rtol * want + LADDER_FLOOR. Every term of the output sum is non-negative, so a relative
+# error per term is at most that relative error of the sum:
+#   fp32-FMA kernels (fp32 P):  the bf16 rounding of the output (u) + the fp32 work (score x scale at arguments up to
+#                               about 260 log2 units, exp, sums of up to 8192 terms, merges: under 1e-4, so 2^-12);
+#   MFMA kernels (bf16 P):      one more u for P rounded to bf16 (the row sum l stays fp32).
+# The floor is for weights below 2^-126 of the maximum, which fp32 and bf16 may flush; nothing else fits under it.
+LADDER_RTOL_FMA = U_BF16 + 2.0 ** -12
+LADDER_RTOL_MMA = 2 * U_BF16 + 2.0 ** -12
+LADDER_FLOOR = 1e-30
+# the shapes the GPU tests run the ladder at (tests/test_exact_gpu.py, tests/test_kv8_gpu.py, test_kv8_split_gpu.py);
+# tests/test_exact_inputs_cpu.py validates the family at every one of them
+LADDER_DECODE_TS = ((40, 17), (384, 256), (1030, 1029))
+LADDER_V4 = (40, 520, 260)  # b, t, slot of the register-ring stream
+LADDER_PREFILL_SHAPES = ((97, 100, False), (130, 10, False), (512, 0, False), (300, 0, True))  # s, slot0, masked
+LADDER_FUSED_TS = ((200, 199), (512, 130))
+LADDER_KV8_SPLIT_TS = ((40, 17), (300, 299), (1030, 700), (8192, 8000))
+
+
+def ladder_levels(profile: str, t: int) -> torch.Tensor:
+    """int64 [t] in 0..128: the level n_j of key j (the number of leading dims on which the key equals u).
+      ramp   j * 128 // (t - 1): the maximum grows in every tile / chunk / split for a positive gain (the newest key
+             dominates); for a negative gain the first valid key is a sink and every later split has m far below M;
+      steps  8 * ((j // 32) % 17): constant over 32 keys, +8 levels per step, then a drop of 128. At gain 8 a step's
+             maximum exceeds the last by 8.16 log2 units (just over the lazy-rescale threshold of 8); at gains -2, 1
+             and 0.25 it stays under it for several steps, so p > 1 drifts up to 2^8 before a rescale;
+      saw    (37 * j) % 129: large jumps both ways inside a tile;
+      high   120 + (5 * j) % 9: with gain +-16 every score sits in +-(170 .. 181) nats."""
+    j = torch.arange(t)
+    if profile == "ramp":
+        return j * 128 // max(t - 1, 1)
+    if profile == "steps":
+        return 8 * ((j // 32) % 17)
+    if profile == "saw":
+        return (37 * j) % 129
+    if profile == "high":
+        return 120 + (5 * j) % 9
+    raise ValueError(profile)
+
+
+def ladder_inputs(b: int, hkv: int, rep: int, t: int, s: int, profile: str, seed: int = 0):
+    """(q bf16 [b, s, h, 128], K bf16 [b, hkv, t, 128], levels int64 [t], gain fp64 [b, s, h]).
+    u[b, kvh] is a seeded +-1 vector; K[b, kvh, j] = u on dims < levels[j] and 0 elsewhere (entries 0 / +-1: exact in
+    bf16 and, at any row scale, in e4m3); q[b, s, h] = gain * u[b, h // rep] with gain = GAINS[(b + s + h + h // rep)
+    % 8], so both signs, sharp and flat, meet in the heads of one kv group and in neighbouring queries. q . k =
+    gain * levels[j] exactly in fp32, in any summation order; the score is that over sqrt(128). V is ``census_v``."""
+    g = torch.Generator().manual_seed(seed)
+    h = hkv * rep
+    u = (torch.randint(0, 2, (b, hkv, DH), generator=g) * 2 - 1).double()
+    levels = ladder_levels(profile, t)
+    assert int(levels.min()) >= 0 and int(levels.max()) <= DH
+    on = torch.arange(DH)[None, :] < levels[:, None]  # [t, 128]
+    kc = (u[:, :, None, :] * on[None, None]).to(BF16)
+    hh = torch.arange(h)
+    idx = (torch.arange(b)[:, None, None] + torch.arange(s)[None, :, None] + (hh + hh // rep)[None, None, :]) % len(GAINS)
+    gain = torch.tensor(GAINS, dtype=torch.float64)[idx]
+    q = (gain[..., None] * u[:, hh // rep][:, None]).to(BF16)
+    return q, kc, levels, gain
+
+
+def ladder_scores(levels: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
+    """fp64 [b, s, h, t]: gain * levels / sqrt(128) in natural units (the product is exact)."""
+    return gain[..., None] * levels.double() / math.sqrt(DH)
+
+
+def ladder_expected(b: int, hkv: int, rep: int, t: int, slot0: int, s: int, kv_start: torch.Tensor, key_mask,
+                    levels: torch.Tensor, gain: torch.Tensor) -> torch.Tensor:
+    """fp64 [b, s, h, 128]: want[b, s, h, cls] = sum of the softmax weights of the valid keys of class cls (the class
+    of ``census_v``), the softmax taken in fp64 over the valid keys of ``valid_keys``; 0 for a query without one."""
+    h = hkv * rep
+    ok = valid_keys(b, t, slot0, s, kv_start, key_mask)[:, :, None, :]  # [b, s, 1, t]
+    sc = ladder_scores(levels, gain).masked_fill(~ok, float("-inf"))
+    mx = sc.amax(-1, keepdim=True)
+    w = torch.exp(sc - torch.where(torch.isfinite(mx), mx, torch.zeros_like(mx)))  # (exp(-inf) = 0 on invalid keys)
+    den = w.sum(-1, keepdim=True)
+    w = torch.where(den > 0, w / den.clamp_min(1e-300), torch.zeros_like(w))
+    cls = _census_class(b, hkv, t).repeat_interleave(rep, dim=1)[:, None].expand(b, s, h, t)
+    return torch.zeros(b, s, h, DH, dtype=torch.float64).scatter_add_(-1, cls, w)
+
+
+def ladder_excess(out: torch.Tensor, want: torch.Tensor, rtol: float) -> torch.Tensor:
+    """fp64 [b, s, h, 128]: |out - want| / (rtol * want + LADDER_FLOOR); inf where it is not a number, or where a
+    query without a valid key is not exactly 0. ``out``: the kernel's [b * s, h * 128] (or [b, s, h * 128])."""
+    o = out.detach().double().cpu().reshape(want.shape)
+    ex = (o - want).abs() / (rtol * want + LADDER_FLOOR)
+    ex = torch.where(torch.isnan(ex), torch.full_like(ex, float("inf")), ex)
+    empty = (want.sum(-1, keepdim=True) == 0) & (o != 0)
+    return torch.where(empty, torch.full_like(ex, float("inf")), ex)
+
+
+def ladder_worst_u(out: torch.Tensor, want: torch.Tensor) -> float:
+    """The largest relative error beyond the floor, (|out - want| - LADDER_FLOOR) / want, in units of u (to report)."""
+    o = out.detach().double().cpu().reshape(want.shape)
+    rel = ((o - want).abs() - LADDER_FLOOR).clamp_min(0)[want > 0] / want[want > 0]
+    return float(rel.max()) / U_BF16 if rel.numel() else 0.0
+
+
+def ladder_mismatch(out: torch.Tensor, want: torch.Tensor, rep: int, rtol: float):
+    """None if every element has |out - want| <= rtol * want + LADDER_FLOOR and the queries without a valid key are
+    exactly 0; else a message naming the first bad (b, s, h, class), observed and expected there and their ratio -- a
+    power of two or e^k points at a rescale that was skipped or applied in the wrong unit."""
+    ex = ladder_excess(out, want, rtol)
+    bad = ~(ex <= 1.0)
+    if not bad.any():
+        return None
+    o = out.detach().double().cpu().reshape(want.shape)
+    bi, si, hi, ci = [int(v) for v in bad.nonzero()[0]]
+    got, exp = float(o[bi, si, hi, ci]), float(want[bi, si, hi, ci])
+    ratio = got / exp if exp != 0 else float("inf" if got != 0 else "nan")
+    logs = (f" (2^{math.log2(ratio):.3f}, e^{math.log(ratio):.3f})" if 0 < ratio < float("inf") else "")
+    return (f"{int(bad.sum())} bad elements, worst |err| / bound {float(ex.max()):.3g}; first at b={bi} s={si} h={hi} "
+            f"(kv head {hi // rep}) class={ci}: observed {got!r}, expected {exp!r}, ratio {ratio:.6g}{logs}")
 
 
 # ----------------------------------------------------------------------------------

@@ -6,7 +6,10 @@ boundary, one K term or column off, a truncated bf16 store or a wrong RoPE table
   A. attention key census  -- q = 0, V = unit vectors of the key's class: ``out * n`` counts the valid keys per class;
   B. attention needle      -- +-1 keys, q = 32 K[j*]: the output is V[j*] bit for bit;
   C. integer GEMM / GEMV   -- every fp32 partial sum exact: the int64 product, round-to-nearest-even bf16 stores with
-                              planted ties, quarter-turn RoPE epilogues, power-of-two fused-norm row scales.
+                              planted ties, quarter-turn RoPE epilogues, power-of-two fused-norm row scales;
+  D. attention ladder      -- exact scores that differ by up to 181 nats: the fp64 softmax per output element to a
+                              relative bound derived from the number formats (A has equal weights and B a single one:
+                              this family guards the weighting -- rescale factors and merge weights between 0 and 1).
 
 Every kernel is forced with the knobs tests/test_kernels_gpu.py uses (restored in ``finally``), and the selection is
 asserted through ``attn_decode_plan_check`` / ``gemm_plan_check``."""
@@ -299,6 +302,151 @@ def test_needle_prefill(impl, rep, s, slot0, masked):
     with _prefill_impl(impl):
         out = _attend(q, kd, vd, slot0, kvs, mask, False)
     assert torch.equal(out.cpu(), want), _needle_report(out, want, jstar, rep)
+
+
+# ---- D. ladder -----------------------------------------------------------------------
+MMA, FMA = xi.LADDER_RTOL_MMA, xi.LADDER_RTOL_FMA  # bf16 P on the matrix cores (2u + 2^-12) / fp32 P (u + 2^-12)
+DECODE_RTOL = {"v2": FMA, "v3": FMA, "v4": FMA, "v5": FMA, "v6": MMA}
+
+
+def _ladder_case(b, hkv, rep, t, slot0, s, kv_start, mask):
+    """{profile: (q on the device, K on the device, want fp64)} and the device V / kv_start / mask they share."""
+    prof = {}
+    for profile in xi.LADDER_PROFILES:
+        q, kc, levels, gain = xi.ladder_inputs(b, hkv, rep, t, s, profile, seed=t + slot0)
+        prof[profile] = (q.to(DEV), kc.to(DEV), xi.ladder_expected(b, hkv, rep, t, slot0, s, kv_start, mask, levels, gain))
+    return prof, xi.census_v(b, hkv, t, DEV), kv_start.to(DEV), None if mask is None else mask.to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _ladder_decode_case(b, hkv, rep, t, slot, masked, kvs_kind):
+    if kvs_kind == "small":
+        kv_start = _small_kv_start(slot)
+    else:
+        kv_start = torch.randint(0, slot // 2, (b,), generator=torch.Generator().manual_seed(3), dtype=torch.int32)
+        kv_start[7] = slot + 1
+    return _ladder_case(b, hkv, rep, t, slot, 1, kv_start, xi.edge_mask(b, t, slot, seed=t + slot) if masked else None)
+
+
+@functools.lru_cache(maxsize=2)  # (the cases run shape by shape: see LADDER_PREFILL_CASES)
+def _ladder_prefill_case(rep, s, slot0, masked):
+    b, hkv = 2, 2
+    t = slot0 + s + 5
+    kv_start = torch.tensor([0, slot0 + s // 3], dtype=torch.int32)
+    return _ladder_case(b, hkv, rep, t, slot0, s, kv_start, xi.edge_mask(b, t, slot0 + s - 1, seed=s) if masked else None)
+
+
+def _assert_ladder(tag, results, rep, rtol):
+    """``results``: (profile, out, want) of one case. Prints the worst relative error in units of u = 2^-8."""
+    worst = {p: xi.ladder_worst_u(out, want) for p, out, want in results}
+    print(f"ladder {tag}: worst relative error {max(worst.values()):.3f} u of the bound {rtol / xi.U_BF16:.4f} u", worst)
+    for profile, out, want in results:
+        msg = xi.ladder_mismatch(out, want, rep, rtol)
+        assert msg is None, f"{profile}: {msg}"
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("t,slot", xi.LADDER_DECODE_TS)
+@pytest.mark.parametrize("kernel,knob,rep", DECODE_KERNELS, ids=_KID)
+def test_ladder_decode(kernel, knob, rep, t, slot, masked):
+    """Scores that differ by design (tests/exact_inputs.py, the ladder) through every small-batch decode kernel: the
+    running maximum moves in every chunk / split / wave (``ramp``), just over and under v6's lazy threshold of 8 log2
+    units (``steps``), both ways inside a tile (``saw``), and sits at +-(170 .. 181) nats (``high``), with gains of both
+    signs in the heads of one kv group. Every element within u + 2^-12 of the fp64 softmax for the fp32-P kernels (v2,
+    v3, v5) and 2u + 2^-12 for v6 (P rounded to bf16 for the matrix cores); the row without a valid key exactly 0."""
+    b, hkv = 3, 2
+    prof, vd, kvs, mask = _ladder_decode_case(b, hkv, rep, t, slot, masked, "small")
+    results = []
+    with _decode_kernel(kernel, knob, b, hkv, t, rep, masked) as packs:
+        for profile, (q, kd, want) in prof.items():
+            results.append((profile, _attend(q, kd, vd, slot, kvs, mask, packs), want))
+    _assert_ladder(f"decode {kernel}", results, rep, DECODE_RTOL[kernel])
+
+
+@pytest.mark.parametrize("rep", [1, 2, 4])
+def test_ladder_decode_v4_midbatch(rep):
+    b, t, slot = xi.LADDER_V4
+    hkv = 2
+    prof, vd, kvs, _ = _ladder_decode_case(b, hkv, rep, t, slot, False, "mid")
+    results = []
+    with _decode_kernel("v4", 0, b, hkv, t, rep, False) as packs:
+        for profile, (q, kd, want) in prof.items():
+            results.append((profile, _attend(q, kd, vd, slot, kvs, None, packs), want))
+    _assert_ladder("decode v4", results, rep, DECODE_RTOL["v4"])
+    assert float(results[0][2][7].abs().max()) == 0  # (row 7 has no valid key)
+
+
+# shape by shape, so that the cached inputs of a (rep, shape) serve every kernel in turn
+LADDER_PREFILL_CASES = [(i, r, s, s0, mk) for s, s0, mk in xi.LADDER_PREFILL_SHAPES for r in (1, 4, 8)
+                        for i in PREFILL_IMPLS if i != 1 or s <= 130]
+
+
+@pytest.mark.parametrize("impl,rep,s,slot0,masked", LADDER_PREFILL_CASES)
+def test_ladder_prefill(impl, rep, s, slot0, masked):
+    """The ladder through every prefill kernel, every query checked: the gain cycles with the query index, so the
+    lanes of one wave need their rescale at different tiles (and the wave-wide ballot of impls 2 / 7 / 8 / 9 / 13 moves
+    a lane's maximum on another lane's account). 2u + 2^-12 for every impl: all of them are matrix-core kernels. Impl
+    1 too rounds P to bf16 for its P.V MFMA (attn_prefill_kernel: ``pw[..] = f2bf(p[n][i])``, the row sum from the
+    fp32 P), the same rounding as the others', so its bound carries that u: measured on an MI355X, impl 1 is
+    off by up to 1.78 u and the impls 2 / 7 / 8 / 9 / 13 by up to 1.88 u."""
+    prof, vd, kvs, mask = _ladder_prefill_case(rep, s, slot0, masked)
+    results = []
+    with _prefill_impl(impl):
+        for profile, (q, kd, want) in prof.items():
+            results.append((profile, _attend(q, kd, vd, slot0, kvs, mask, False), want))
+    _assert_ladder(f"prefill impl {impl}", results, rep, MMA)
+
+
+@pytest.mark.parametrize("spl", [1, 2])
+@pytest.mark.parametrize("b,hkv,rep", [(1, 1, 8), (3, 1, 8), (2, 8, 4)])
+@pytest.mark.parametrize("t,slot", xi.LADDER_FUSED_TS)
+def test_ladder_fused_qkv_attention_launch(b, hkv, rep, t, slot, spl):
+    """The fused qkv + attention launch (128-key splits, merged by the last arriver) on the ladder, built like
+    test_census_fused_qkv_attention_launch: row r of x is e_r and column r of W holds row r's q | k | v of the new
+    slot, so the launch itself produces the ladder query and writes the new key at its level and its census V row. The
+    RoPE table is the quarter-turn table with the row of the new position set to the identity (a whole turn), every
+    other row a real rotation. 2u + 2^-12 (bf16 P); the caches afterwards hold the ladder keys and the census bit for
+    bit."""
+    e = ops.ext()
+    k = 1024
+    h = hkv * rep
+    n = (h + 2 * hkv) * DH
+    kv_start = (torch.tensor([0, 37, slot + 1] + [5 * i % 60 for i in range(b)], dtype=torch.int32)[:b]
+                if b > 1 else torch.tensor([3], dtype=torch.int32))
+    v_full = xi.census_v(b, hkv, t)
+    table = xi.quarter_table(NPOS)
+    table[slot] = torch.tensor([1.0, 0.0])
+    table = table.to(DEV)
+    pos = torch.full((b,), slot, dtype=torch.int32, device=DEV)
+    sl = torch.tensor([slot], dtype=torch.int32, device=DEV)
+    xd = torch.zeros(b, k, dtype=BF16)
+    xd[torch.arange(b), torch.arange(b)] = 1
+    xd = xd.to(DEV)
+    splits = e.qkv_attn_splits(b, b, hkv, rep, t, n, ops._num_cus(xd.device), spl)
+    if spl == 2 and splits == 0:
+        assert e.qkv_attn_splits(b, b, hkv, rep, t, n, ops._num_cus(xd.device), 1) > 0
+        pytest.skip("the split qkv grid does not fit the CUs")
+    assert splits == (t + 127) // 128
+    results = []
+    for profile in xi.LADDER_PROFILES:
+        q, kc, levels, gain = xi.ladder_inputs(b, hkv, rep, t, 1, profile, seed=t + slot)
+        want = xi.ladder_expected(b, hkv, rep, t, slot, 1, kv_start, None, levels, gain)
+        w = torch.zeros(n, k, dtype=BF16)
+        w[:h * DH, :b] = q.reshape(b, h * DH).t()
+        w[h * DH:(h + hkv) * DH, :b] = kc[:, :, slot].reshape(b, hkv * DH).t()
+        w[(h + hkv) * DH:, :b] = v_full[:, :, slot].reshape(b, hkv * DH).t()
+        kc0, vc0 = kc.clone(), v_full.clone()
+        kc0[:, :, slot] = 7.0   # stale rows at the new key's slot: the launch must overwrite both
+        vc0[:, :, slot] = 0.5
+        kd, vd = kc0.to(DEV), vc0.to(DEV)
+        packed = ops.packed_empty(b, h * DH, DEV)
+        out = ops.linear_qkv_attention(xd, PackedLinear.from_dense(w, DEV), None, table, pos, kd, vd, sl,
+                                       kv_start.to(DEV), h, hkv, DH, splits, out_packed=packed, spl=spl)
+        torch.cuda.synchronize()
+        assert torch.equal(ref.unpack_act(packed.cpu(), b), out.cpu())
+        assert torch.equal(vd.cpu(), v_full) and torch.equal(kd.cpu(), kc), profile
+        results.append((profile, out, want))
+    _assert_ladder("fused qkv + attention", results, rep, MMA)
 
 
 # ======================================================================================

@@ -2,6 +2,8 @@
 tests (tests/test_exact_gpu.py) assert about the kernels holds for the reference, with the margins the bounds assume."""
 from __future__ import annotations
 
+import math
+
 import pytest
 import torch
 
@@ -95,6 +97,143 @@ def test_needle_weights_exactly_one_hot(t, slot0, s, masked):
     else:  # every query's diagonal key is some head's needle at the queries where the cycle starts there
         diag = (jstar == (slot0 + torch.arange(s))[None, :, None]).any(-1)
         assert int(diag.sum()) > 0
+
+
+# ---- the ladder ------------------------------------------------------------------------
+def _ladder_shapes():
+    """(b, hkv, rep, t, slot0, s, kv_start kind, masked) of every shape and mask the GPU tests run the ladder at
+    (one rep each: the reference and the loop below treat every head alike)."""
+    out = []
+    for t, slot in dict.fromkeys(xi.LADDER_DECODE_TS + xi.LADDER_KV8_SPLIT_TS):
+        out += [(3, 2, 4, t, slot, 1, "small", masked) for masked in (False, True)]
+    out.append((xi.LADDER_V4[0], 2, 2, xi.LADDER_V4[1], xi.LADDER_V4[2], 1, "mid", False))
+    out += [(2, 2, 4, slot0 + s + 5, slot0, s, "prefill", masked) for s, slot0, masked in xi.LADDER_PREFILL_SHAPES]
+    out += [(b, hkv, rep, t, slot, 1, "fused", False) for b, hkv, rep in ((1, 1, 8), (3, 1, 8), (2, 8, 4))
+            for t, slot in xi.LADDER_FUSED_TS]
+    return out
+
+
+def _ladder_kv_start(kind, b, slot0, s):
+    """The kv_start vectors of the GPU tests (test_exact_gpu.py, test_kv8_gpu.py), by kind."""
+    if kind == "small":
+        return torch.tensor([0, 37, slot0 + 1], dtype=torch.int32)
+    if kind == "mid":
+        kv_start = torch.randint(0, slot0 // 2, (b,), generator=torch.Generator().manual_seed(3), dtype=torch.int32)
+        kv_start[7] = slot0 + 1
+        return kv_start
+    if kind == "prefill":
+        return torch.tensor([0, slot0 + s // 3], dtype=torch.int32)
+    return (torch.tensor([0, 37, slot0 + 1] + [5 * i % 60 for i in range(b)], dtype=torch.int32)[:b]
+            if b > 1 else torch.tensor([3], dtype=torch.int32))
+
+
+def _lazy_rescale_loop(q, kc, cls, ok, rescale=True):
+    """The lazy-rescale online softmax of the MFMA kernels in plain tensor steps: 32-key tiles, log2 units, the running
+    maximum moves only when some head of the query sees a tile maximum more than 8 above its own (the wave-wide
+    ballot), P rounded to bf16 for the P.V sum, the row sum l in fp32 from the unrounded P. ``cls`` [b, h, t]: the
+    class of each key's unit V row; ``ok`` [b, s, t]. ``rescale`` False leaves l and O as they are when the maximum
+    moves -- the bug the family has to catch. Returns bf16 [b, s, h, 128]."""
+    b, s, h, _ = q.shape
+    t = kc.shape[2]
+    rep = h // kc.shape[1]
+    scale_log2 = torch.tensor(math.log2(math.e) / math.sqrt(xi.DH), dtype=torch.float32)
+    kf = kc.float().repeat_interleave(rep, dim=1)
+    dots = torch.einsum("bshd,bhtd->bsht", q.float(), kf)  # exact in fp32
+    sc_all = (dots * scale_log2).masked_fill(~ok[:, :, None, :], float("-inf"))
+    m = torch.full((b, s, h), float("-inf"))
+    l = torch.zeros(b, s, h)
+    o = torch.zeros(b, s, h, xi.DH)
+    for k0 in range(0, t, 32):
+        sc = sc_all[..., k0:k0 + 32]
+        tmax = sc.amax(-1)
+        trig = (tmax > m + 8.0).any(-1, keepdim=True)
+        m_new = torch.where(trig, torch.maximum(m, tmax), m)
+        alpha = torch.exp2(m - torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new))
+        alpha = torch.where(torch.isnan(alpha), torch.ones_like(alpha), alpha)
+        if rescale:
+            l = l * alpha
+            o = o * alpha[..., None]
+        m = m_new
+        p = torch.exp2(sc - torch.where(torch.isinf(m), torch.zeros_like(m), m)[..., None])
+        l = l + p.sum(-1)
+        o.scatter_add_(-1, cls[:, None, :, k0:k0 + 32].expand(b, s, h, -1), p.to(BF16).float())
+    out = torch.where(l[..., None] > 0, o / l[..., None].clamp_min(1e-38), torch.zeros_like(o))
+    return out.to(BF16)
+
+
+@pytest.mark.parametrize("b,hkv,rep,t,slot0,s,kind,masked", _ladder_shapes())
+def test_ladder_family(b, hkv, rep, t, slot0, s, kind, masked):
+    """What the GPU ladder tests rest on, at each of their shapes and masks and for every profile: the scores of the
+    bf16 tensors are gain * level / sqrt(128) bit for bit; ``ref.attention`` (fp32) is within u + 2^-12 of the fp64
+    softmax per element and exactly 0 where a query has no key; the keys survive the fp8 round trip; a lazy-rescale loop
+    with bf16 P is within 2u + 2^-12 -- and the same loop without the rescale of l and O misses that bound by a factor
+    of 1000 or more on ``ramp``, ``steps`` and ``saw`` wherever a query's keys span more than one tile.
+
+    One shape cannot reach the factor 1000 whatever a loop does wrong, the unmasked 8001 keys of the t = 8192 cache
+    with their 62 keys of every class: ``ramp`` there holds 64 keys per level, so even at gain 16 a whole period of the
+    128 classes spans 4.2 log2 units and the smallest class weight is about 1 / 770, while the loop without the rescale
+    weighs every stretch between two moves of the maximum alike, near 1 / 128 per class: 5 times the smallest weight,
+    600 times the bound at the very most (411 here). ``steps`` repeats every 544 keys, the maximum stops moving inside
+    the first period, and the 14 periods that follow are weighed correctly: the error is one period's share, 22 times
+    the bound. These two must still miss the bound 10 times over; with the mask (some classes keep few keys) and on
+    ``saw`` the factor 1000 holds there too."""
+    import kv8_inputs as k8
+    h = hkv * rep
+    kv_start = _ladder_kv_start(kind, b, slot0, s)
+    mask = xi.edge_mask(b, t, slot0 + s - 1, seed=s if kind == "prefill" else t + slot0) if masked else None
+    ok = xi.valid_keys(b, t, slot0, s, kv_start, mask)
+    tiles = torch.nn.functional.pad(ok, (0, -t % 32)).reshape(b, s, -1, 32).any(-1).sum(-1)  # 32-key tiles per query
+    if kind != "fused" or b == 3:
+        assert int(ok.sum(-1).min()) == 0  # a query without a valid key is among them
+    vc = xi.census_v(b, hkv, t)
+    cls = xi._census_class(b, hkv, t).repeat_interleave(rep, dim=1)
+    for profile in xi.LADDER_PROFILES:
+        q, kc, levels, gain = xi.ladder_inputs(b, hkv, rep, t, s, profile, seed=t + slot0)
+        assert set(gain.unique().tolist()) <= set(xi.GAINS) and torch.equal(q.double().abs().amax(-1), gain.abs())
+        assert s == 1 or len(gain.unique()) == len(xi.GAINS)
+        want = xi.ladder_expected(b, hkv, rep, t, slot0, s, kv_start, mask, levels, gain)
+        tot = want.sum(-1)
+        assert bool(((tot - 1).abs() < 1e-12)[ok.any(-1)].all()) and bool((tot[~ok.any(-1)] == 0).all())
+        # the scores, recomputed from the tensors the kernels read
+        sc = torch.einsum("bshd,bhtd->bsht", q.double(), kc.double().repeat_interleave(rep, dim=1)) / math.sqrt(xi.DH)
+        assert torch.equal(sc, xi.ladder_scores(levels, gain))
+        # the fp32 reference
+        out = ref.attention(q, kc, vc, slot0, kv_start, mask)
+        msg = xi.ladder_mismatch(out, want, rep, xi.LADDER_RTOL_FMA)
+        assert msg is None, (profile, msg)
+        assert bool((out.reshape(b, s, -1)[~ok.any(-1)] == 0).all())
+        # the fp8 cache holds the same keys
+        k8q = k8.quantize_kv(kc)
+        assert torch.equal(k8q.dequant(), kc) and torch.equal(k8.quantize_kv(vc).dequant(), vc)
+        # sensitivity
+        lazy = _lazy_rescale_loop(q, kc, cls, ok)
+        msg = xi.ladder_mismatch(lazy, want, rep, xi.LADDER_RTOL_MMA)
+        assert msg is None, (profile, msg)
+        broken = _lazy_rescale_loop(q, kc, cls, ok, rescale=False)
+        worst = float(xi.ladder_excess(broken, want, xi.LADDER_RTOL_MMA).max())
+        print(f"{profile}: reference {xi.ladder_worst_u(out, want):.2f} u, lazy loop {xi.ladder_worst_u(lazy, want):.2f} u, "
+              f"loop without the rescale {worst:.3g} x the bound")
+        if profile != "high" and int(tiles.max()) > 1:
+            assert worst >= (10 if t == 8192 and not masked and profile != "saw" else 1000), (profile, worst)
+
+
+def test_ladder_mismatch_reports():
+    b, hkv, rep, t, slot = 3, 2, 4, 384, 256
+    kv_start = torch.tensor([0, 37, slot + 1], dtype=torch.int32)
+    q, kc, levels, gain = xi.ladder_inputs(b, hkv, rep, t, 1, "steps", seed=1)
+    want = xi.ladder_expected(b, hkv, rep, t, slot, 1, kv_start, None, levels, gain)
+    good = want.float().to(BF16).reshape(b, -1)
+    assert xi.ladder_mismatch(good, want, rep, xi.LADDER_RTOL_FMA) is None and xi.ladder_worst_u(good, want) <= 1.0
+    bad = good.clone().float()
+    bad[1, 3 * xi.DH: 4 * xi.DH] *= 2  # head 3 of row 1 twice too large: a skipped rescale by one log2 unit
+    msg = xi.ladder_mismatch(bad, want, rep, xi.LADDER_RTOL_MMA)
+    assert msg is not None and "b=1 s=0 h=3" in msg and "ratio 2" in msg and "2^1.0" in msg
+    leak = good.clone()
+    leak[2, 5] = 1e-20  # the row without a valid key must be exactly 0
+    assert "b=2" in xi.ladder_mismatch(leak, want, rep, xi.LADDER_RTOL_MMA)
+    nan = good.clone().float()
+    nan[0, 0] = float("nan")
+    assert xi.ladder_mismatch(nan, want, rep, xi.LADDER_RTOL_MMA) is not None
 
 
 @pytest.mark.parametrize("m,n,k", [(1, 768, 256), (17, 48, 4096), (200, 768, 1024), (129, 1040, 96)])

@@ -276,6 +276,51 @@ def test_decode_attention(waves, rep, t, slot, masked):
         _check_decode_case(case, b, hkv, rep, slot)
 
 
+@functools.lru_cache(maxsize=None)
+def _ladder_case(b, hkv, rep, t, slot, masked):
+    """Shared, read-only: the ladder of tests/exact_inputs.py on an fp8 cache (its keys are 0 / +-1 and its V rows unit
+    vectors: the quantiser loses nothing), per profile (q, K) on the device and the fp64 softmax; V, kv_start, mask."""
+    kv_start = _kv_start(b, slot)
+    mask = xi.edge_mask(b, t, slot, seed=t + slot) if masked else None
+    prof = {}
+    for profile in xi.LADDER_PROFILES:
+        q, kc, levels, gain = xi.ladder_inputs(b, hkv, rep, t, 1, profile, seed=t + slot)
+        kq = k8.quantize_kv(kc)
+        assert torch.equal(kq.dequant(), kc)
+        prof[profile] = (q.to(DEV), k8.to_device(kq, DEV),
+                         xi.ladder_expected(b, hkv, rep, t, slot, 1, kv_start, mask, levels, gain))
+    vq = k8.quantize_kv(xi.census_v(b, hkv, t))
+    return prof, k8.to_device(vq, DEV), kv_start.to(DEV), None if mask is None else mask.to(DEV)
+
+
+def _check_ladder_case(case, rep, slot, tag):
+    """Every element within u + 2^-12 of the fp64 softmax (fp32 P and fp32 FMAs; u is the bf16 rounding of the output),
+    the row without a valid key exactly 0. Prints the worst relative error in units of u = 2^-8."""
+    prof, vq, kvs, mask = case
+    results = [(profile, _attend(q, kq, vq, slot, kvs, mask), want) for profile, (q, kq, want) in prof.items()]
+    worst = {p: xi.ladder_worst_u(out, want) for p, out, want in results}
+    print(f"ladder {tag}: worst relative error {max(worst.values()):.3f} u of the bound "
+          f"{xi.LADDER_RTOL_FMA / xi.U_BF16:.4f} u", worst)
+    for profile, out, want in results:
+        msg = xi.ladder_mismatch(out, want, rep, xi.LADDER_RTOL_FMA)
+        assert msg is None, f"{profile}: {msg}"
+    assert float(results[0][2][2].abs().max()) == 0  # (row 2 has no valid key)
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("t,slot", xi.LADDER_DECODE_TS)
+@pytest.mark.parametrize("rep", [1, 2, 4, 8])
+@pytest.mark.parametrize("waves", [8, 1])
+def test_decode_attention_ladder(waves, rep, t, slot, masked):
+    """Scores with a real range (up to 181 nats between two keys, gains of both signs within a kv group) on the fp8
+    cache, both wave forms: the running maximum moves in every chunk and the wave merge weighs partials whose maxima
+    are far apart. The census above has equal weights and the needles a single one."""
+    b, hkv = 3, 2
+    case = _ladder_case(b, hkv, rep, t, slot, masked)
+    with _waves(waves, b, hkv, rep, t, masked):
+        _check_ladder_case(case, rep, slot, f"fp8 decode waves {waves}")
+
+
 def test_decode_attention_one_wave_1024_pairs():
     b, hkv, rep, t, slot = 128, 8, 4, 300, 299
     case = _decode_case(b, hkv, rep, t, slot, False)

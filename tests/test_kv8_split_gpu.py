@@ -80,6 +80,26 @@ def test_decode_attention_split(rep, t, slot, splits, masked):
         base._check_decode_case(case, B, HKV, rep, slot)
 
 
+SPLIT_CASES = [(40, 17, 4), (300, 299, 2), (300, 299, 3), (1030, 700, 7), (8192, 8000, 0)]
+assert tuple(dict.fromkeys((t, s) for t, s, _ in SPLIT_CASES)) == xi.LADDER_KV8_SPLIT_TS
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("t,slot,splits", SPLIT_CASES)
+@pytest.mark.parametrize("rep", [1, 2, 4, 8])
+def test_decode_attention_split_ladder(rep, t, slot, splits, masked):
+    """The ladder (tests/exact_inputs.py) through the key-split merge, at the split counts of the test above: with
+    ``ramp`` a negative gain puts all the weight into the first split and a positive one into the last, so every other
+    partial is merged with exp2(m - M) far from 1 (the census merges equal maxima, the needle a factor of exactly 0).
+    Every element within u + 2^-12 of the fp64 softmax."""
+    case = base._ladder_case(B, HKV, rep, t, slot, masked)
+    with _splits(splits) as e:
+        rc, why, nsplit, *_ = e.attn_decode_q8_split_check(B, HKV * rep, HKV, DH, t, masked)
+        assert rc == 0, why
+        assert nsplit > 1 if splits == 0 else nsplit == _expected_pinned(t, rep, splits)
+        base._check_ladder_case(case, rep, slot, f"fp8 split {nsplit}")
+
+
 # ---------------------------------------------------------------------------------- geometry (no launch)
 def test_split_geometry():
     e = ops.ext()
