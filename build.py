@@ -71,6 +71,10 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-munsafe-f
              "-Wno-unused-result", "-D__HIP_PLATFORM_AMD__"]
 
 
+# Per-file flags, by source stem. gemm_wq: built without the packed fp32 VALU ops (v_pk_fma_f32 and kin).
+FILE_FLAGS = {"gemm_wq": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
+
+
 def _scratch_users(remarks: str):
     """Kernels whose resource-usage remark reports scratch (private) memory: on these kernels that
     means a runtime-indexed register array or a spill -- almost always a large slowdown."""
@@ -94,8 +98,8 @@ SCRATCH_OK: dict = {}
 def _compile_hip(src: Path, obj: Path, headers, force: bool, extra=()):
     if force or _stale(obj, [src, *headers]):
         obj.parent.mkdir(parents=True, exist_ok=True)
-        out = _run([HIPCC, *HIP_FLAGS, *extra, "-Rpass-analysis=kernel-resource-usage", "-c", str(src), "-o",
-                    str(obj)])
+        out = _run([HIPCC, *HIP_FLAGS, *FILE_FLAGS.get(src.stem, []), *extra, "-Rpass-analysis=kernel-resource-usage",
+                    "-c", str(src), "-o", str(obj)])
         bad = [(n, b) for n, b in _scratch_users(out) if not any(ok in n and b <= lim for ok, lim in SCRATCH_OK.items())]
         if bad:
             obj.unlink(missing_ok=True)

@@ -11,7 +11,7 @@ random-init model of a named architecture with synthetic prompt ids (no checkpoi
 
   python examples/generate.py --ckpt_dir /ckpt/8B --tokenizer_path /ckpt/tokenizer.model --is_llama3
   torchrun --nproc-per-node 8 --master-addr 127.0.0.1 examples/generate.py --ckpt_dir /ckpt/70B ...
-  python examples/generate.py --synthetic --model llama3-8b --max_gen_len 32 [--weights fp8|mxfp4]
+  python examples/generate.py --synthetic --model llama3-8b --max_gen_len 32 [--weights fp8|mxfp4 [--quantized-gemm direct]]
 """
 from __future__ import annotations
 
@@ -36,11 +36,13 @@ WEIGHT_FORMATS = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4"}  # --weights -> LLaMAForC
 
 
 def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int = 2048, weights: str = "bf16",
-         kv_cache: str = "bf16", **model_kwargs) -> LLaMA:
+         kv_cache: str = "bf16", quantized_gemm: str = "dequant", **model_kwargs) -> LLaMA:
     """Reference ``load`` (jax_example.py:10-31) on the MI355X runtime. ``weights="fp8"`` / ``"mxfp4"``: the layer
     projections are quantised to FP8 e4m3 / MXFP4 after loading (``LLaMAForCausalLM.quantize_weights_``; each rank its
     own shard).
-    ``kv_cache="fp8"``: the KV caches hold FP8 e4m3 rows (``LLaMAForCausalLM.set_kv_cache_format``)."""
+    ``kv_cache="fp8"``: the KV caches hold FP8 e4m3 rows (``LLaMAForCausalLM.set_kv_cache_format``).
+    ``quantized_gemm="direct"``: quantised projections stream their bytes at 65 .. 512 rows too
+    (``LLaMAForCausalLM.set_quantized_gemm``)."""
     ctx = init_distributed()
     ctx.setup_mesh(tp=ctx.world)
     with open(os.path.join(ckpt_dir, "params.json")) as f:
@@ -53,6 +55,7 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
     del params
     if weights != "bf16":
         model.quantize_weights_(WEIGHT_FORMATS[weights])
+        model.set_quantized_gemm(quantized_gemm)
     if kv_cache == "fp8":
         model.set_kv_cache_format("fp8_e4m3")
     return LLaMA(None, model, tokenizer, mesh=Mesh(dp=1, mp=ctx.tp_size, rank=ctx.rank))
@@ -60,10 +63,12 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
 
 def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int = 256, temperature: float = 0.8,
          top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1,
-         repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0):
+         repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
+         quantized_gemm: str = "dequant"):
     """Reference ``main`` (jax_example.py:33-40). ``num_beams > 1``: beam search (temperature is then taken as 0).
     Llama-3 (without beam search) stops on any of the tokenizer's ``stop_tokens`` (end of text, end of turn)."""
-    generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache)
+    generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache,
+                     quantized_gemm=quantized_gemm)
     if num_beams > 1:
         temperature = 0.0
     stops = sorted(generator.tokenizer.stop_tokens) if is_llama3 and num_beams == 1 else None
@@ -80,7 +85,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
               weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1, repetition_penalty: float = 1.0,
-              no_repeat_ngram_size: int = 0, min_new_tokens: int = 0):
+              no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, quantized_gemm: str = "dequant"):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -90,6 +95,7 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
     model = LLaMAForCausalLM(cfg, device=ctx.device, comm=comm, _do_init=False).init_random(seed=0)
     if weights != "bf16":
         model.quantize_weights_(WEIGHT_FORMATS[weights])
+        model.set_quantized_gemm(quantized_gemm)
     if kv_cache == "fp8":
         model.set_kv_cache_format("fp8_e4m3")
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
@@ -123,6 +129,9 @@ if __name__ == "__main__":
     ap.add_argument("--weights", choices=["bf16", "fp8", "mxfp4"], default="bf16",
                     help="fp8: FP8 e4m3 weight-only layer projections (one power-of-two scale per output row); "
                     "mxfp4: 4-bit e2m1 codes with one power-of-two scale per row and 32 K elements")
+    ap.add_argument("--quantized-gemm", choices=["dequant", "direct"], default="dequant",
+                    help="fp8 / mxfp4 weights at 65 .. 512 rows: dequantise then the bf16 GEMM, or the GEMM that streams "
+                    "the quantised bytes (LLaMAForCausalLM.set_quantized_gemm)")
     ap.add_argument("--kv-cache", choices=["bf16", "fp8"], default="bf16",
                     help="fp8: KV caches of FP8 e4m3 rows (one power-of-two scale per row, kv head and slot): 132 bytes "
                     "per 128-value row instead of 256")
@@ -137,9 +146,9 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.synthetic:
         synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
-                  a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens)
+                  a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
         main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
-             a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens)
+             a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm)

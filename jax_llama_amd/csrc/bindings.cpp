@@ -559,6 +559,52 @@ void gemm_qkv(Tensor x, Tensor w, int64_t n, int64_t k, Tensor table, Tensor pos
           "gemm_qkv");
 }
 
+// ---- The quantised-weight GEMM (kernels/gemm5q.h) for 64 < M <= WQ_GEMM_MAX_M: fmt WQ_FP8 (wq / sc as
+// check_packed_w8) or WQ_MXFP4 (as check_packed_w4). tile / ksplit <= 0: gemm_wq_plan()'s default plan. ws: the slab
+// workspace, gemm_wq_ksplit() x M x (N + 1) floats.
+static void check_wq(const Tensor& x, const Tensor& wq, const Tensor& sc, int64_t fmt, int64_t n, int64_t k, int64_t mode,
+                     double rms_eps, int64_t ksplit, int64_t tile, const Tensor& ws) {
+  check_gpu(x, "x");
+  check(fmt == jla::WQ_FP8 || fmt == jla::WQ_MXFP4, "gemm_wq fmt: WQ_FP8 or WQ_MXFP4");
+  if (fmt == jla::WQ_FP8)
+    check_packed_w8(wq, sc, n, k);
+  else
+    check_packed_w4(wq, sc, n, k);
+  check(x.dim() == 2 && x.size(1) == k && x.scalar_type() == torch::kBFloat16, "x must be bf16 [M, K]");
+  const int64_t m = x.size(0);
+  const jla::GemmPlanResult r = jla::gemm_wq_plan((int)m, (int)n, (int)k, (int)mode, rms_eps >= 0, (int)fmt, (int)ksplit,
+                                                  (int)tile, jla::gemm_num_cus());
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: gemm_wq: no plan for this call (gemm_wq_plan, gemm_plan.h: rc ", r.rc, ")");
+  check_gpu(ws, "gemm_wq ws");
+  check(ws.scalar_type() == torch::kFloat32 && ws.numel() >= r.plan.ksplit * m * (n + (rms_eps >= 0 ? 1 : 0)),
+        "gemm_wq ws too small");
+}
+
+void gemm_wq(Tensor x, Tensor wq, Tensor sc, int64_t fmt, int64_t n, int64_t k, Tensor out, int64_t mode,
+             bool accumulate, c10::optional<Tensor> mirror, int64_t ksplit, int64_t tile, Tensor ws, double rms_eps) {
+  check(mode >= 0 && mode <= 2, "gemm_wq mode");
+  check_wq(x, wq, sc, fmt, n, k, mode, rms_eps, ksplit, tile, ws);
+  const int64_t m = x.size(0);
+  check_linear_out(out, m, n, mode);
+  jla::bf16_t* mir = mode == 1 ? mirror_ptr(mirror, out.numel()) : nullptr;
+  gemm_rc(jla::gemm_wq(cbf(x), wq.data_ptr(), sc.data_ptr(), (int)fmt, out.data_ptr(), m, n, k, mode, accumulate,
+                       out.scalar_type() == torch::kFloat32, mir, nullptr, ptr<float>(ws), ws.numel(), (int)ksplit,
+                       (int)tile, (float)rms_eps, stream()),
+          "gemm_wq");
+}
+
+// ... with the RoPE + KV-cache write in the reduce epilogue (as gemm_qkv under a K split)
+void gemm_wq_qkv(Tensor x, Tensor wq, Tensor sc, int64_t fmt, int64_t n, int64_t k, Tensor table, Tensor positions,
+                 Tensor kc, Tensor vc, Tensor slot, int64_t seq_len, int64_t h, int64_t hkv, int64_t dh, Tensor q,
+                 int64_t ksplit, int64_t tile, Tensor ws, double rms_eps) {
+  check_wq(x, wq, sc, fmt, n, k, MODE_QKV, rms_eps, ksplit, tile, ws);
+  const int64_t m = x.size(0);
+  jla::QKVArgs qa = qkv_args(m, n, table, positions, kc, vc, slot, seq_len, h, hkv, dh, q);
+  gemm_rc(jla::gemm_wq(cbf(x), wq.data_ptr(), sc.data_ptr(), (int)fmt, nullptr, m, n, k, MODE_QKV, 0, 0, nullptr, &qa,
+                       ptr<float>(ws), ws.numel(), (int)ksplit, (int)tile, (float)rms_eps, stream()),
+          "gemm_wq_qkv");
+}
+
 void rope_kv_write(Tensor qkv, Tensor table, Tensor positions, Tensor kc, Tensor vc, Tensor slot, int64_t seq_len,
                    int64_t h, int64_t hkv, int64_t dh, Tensor q) {
   for (auto* t : {&qkv, &table, &positions, &kc, &vc, &slot, &q}) check_gpu(*t, "rope_kv_write arg");
@@ -1217,6 +1263,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
         py::arg("positions"), py::arg("kc"), py::arg("vc"), py::arg("slot"), py::arg("seq_len"), py::arg("h"),
         py::arg("hkv"), py::arg("dh"), py::arg("q"), py::arg("ksplit"), py::arg("ws"), py::arg("rms_eps") = -1.0,
         py::arg("tile") = 0, py::arg("rms_ws") = py::none());
+  // the quantised-weight GEMM (kernels/gemm5q.h); gemm_wq_plan_check: gemm_wq_plan()'s return code on this device
+  // (0: gemm_wq runs the call); gemm_wq_ksplit: the plan's effective split (the slab count of its workspace; 0: no plan)
+  m.def("gemm_wq", &gemm_wq, py::arg("x"), py::arg("wq"), py::arg("sc"), py::arg("fmt"), py::arg("n"), py::arg("k"),
+        py::arg("out"), py::arg("mode"), py::arg("accumulate"), py::arg("mirror"), py::arg("ksplit"), py::arg("tile"),
+        py::arg("ws"), py::arg("rms_eps") = -1.0);
+  m.def("gemm_wq_qkv", &gemm_wq_qkv, py::arg("x"), py::arg("wq"), py::arg("sc"), py::arg("fmt"), py::arg("n"),
+        py::arg("k"), py::arg("table"), py::arg("positions"), py::arg("kc"), py::arg("vc"), py::arg("slot"),
+        py::arg("seq_len"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("q"), py::arg("ksplit"),
+        py::arg("tile"), py::arg("ws"), py::arg("rms_eps") = -1.0);
+  m.def("gemm_wq_plan_check", [](int64_t m, int64_t n, int64_t k, int64_t mode, bool rms, int64_t fmt, int64_t ksplit,
+                                 int64_t tile) {
+    return jla::gemm_wq_plan_check((int)m, (int)n, (int)k, (int)mode, rms, (int)fmt, (int)ksplit, (int)tile);
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("mode"), py::arg("rms"), py::arg("fmt"), py::arg("ksplit") = 0,
+     py::arg("tile") = 0);
+  m.def("gemm_wq_ksplit", [](int64_t m, int64_t n, int64_t k, int64_t mode, int64_t fmt, int64_t ksplit, int64_t tile) {
+    return jla::gemm_wq_ksplit((int)m, (int)n, (int)k, (int)mode, (int)fmt, (int)ksplit, (int)tile);
+  }, py::arg("m"), py::arg("n"), py::arg("k"), py::arg("mode"), py::arg("fmt"), py::arg("ksplit") = 0,
+     py::arg("tile") = 0);
+  m.attr("WQ_FP8") = jla::WQ_FP8;
+  m.attr("WQ_MXFP4") = jla::WQ_MXFP4;
+  m.attr("WQ_GEMM_MAX_M") = jla::WQ_GEMM_MAX_M;
   m.def("gemm_argmax", &gemm_argmax, py::arg("x"), py::arg("w"), py::arg("n"), py::arg("k"), py::arg("ws"),
         py::arg("rms_eps"), py::arg("idx"), py::arg("val"), py::arg("rms_ws") = py::none());
   m.def("gemm_argmax_workspace", [](int64_t m, int64_t n) { return (int64_t)jla::gemm_argmax_workspace_floats(m, n); });

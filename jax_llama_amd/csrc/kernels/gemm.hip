@@ -1635,6 +1635,33 @@ int gemm(const bf16_t* x, const void* W, void* out, int M, int N, int K, int mod
   return launch_reduce(ws, p.ksplit, out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ssq, rms_eps, s);
 }
 
+// ---- The quantised-weight GEMM: gemm5q's partial kernel on the FP8 / MXFP4 bytes (gemm5q.h; gemm_wq.hip launches
+// it), then the reduce kernel with the caller's epilogue, exactly as a gemm5 plan. gemm_wq_plan() (gemm_plan.h) is the
+// one rule.
+int gemm_wq_plan_check(int M, int N, int K, int mode, int rms, int fmt, int ksplit, int tile) {
+  return gemm_wq_plan(M, N, K, mode, rms != 0, fmt, ksplit, tile, num_cus()).rc;
+}
+
+int gemm_wq_ksplit(int M, int N, int K, int mode, int fmt, int ksplit, int tile) {
+  const GemmPlanResult r = gemm_wq_plan(M, N, K, mode, false, fmt, ksplit, tile, num_cus());
+  return r.rc == 0 ? r.plan.ksplit : 0;
+}
+
+int gemm_wq(const bf16_t* x, const void* Wq, const void* S, int fmt, void* out, int M, int N, int K, int mode,
+            int accumulate, int out_f32, bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit,
+            int tile, float rms_eps, hipStream_t s) {
+  const GemmPlanResult r = gemm_wq_plan(M, N, K, mode, rms_eps >= 0.f, fmt, ksplit, tile, num_cus());
+  const GemmPlan& p = r.plan;
+  if (r.rc != 0) return r.rc;
+  if (mode == MODE_QKV && !qkv) return -1;
+  // workspace: [ksplit][M][N] fp32 partial slabs, then (fused norm) [ksplit][M] partial sums of squares
+  const size_t slabs = (size_t)p.ksplit * M * N;
+  if (ws == nullptr || ws_floats < slabs + (p.norm != NORM_NONE ? (size_t)p.ksplit * M : 0)) return -3;
+  float* ssq = p.norm != NORM_NONE ? ws + slabs : nullptr;
+  if (int e = gemm5q_launch(x, Wq, S, fmt, ws, M, N, K, ssq, p.nj, p.ksplit, p.kc, s)) return e;
+  return launch_reduce(ws, p.ksplit, out, M, N, K, mode, accumulate, out_f32, mirror, qkv, ssq, rms_eps, s);
+}
+
 // ---- greedy lm_head: GEMM with the argmax in its epilogue (no fp32 logits round trip through HBM:
 // at M = 2048, V = 128256 that is 1 GB written + 1 GB read per decode step), then the [M][P] partials are
 // reduced per row. Ties go to the smaller index, so the result equals argmax_kernel's.

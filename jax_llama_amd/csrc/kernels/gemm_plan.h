@@ -195,4 +195,51 @@ inline GemmPlanResult gemm_plan(int M, int N, int K, int mode, bool rms, int ksp
   return {0, p};
 }
 
+// ---- The quantised-weight GEMM (gemm5q.h): gemm5's workgroup on the FP8 / MXFP4 bytes, for the rows above the
+// decode GEMVs' 64. Weight formats (the `fmt` argument):
+constexpr int WQ_FP8 = 1, WQ_MXFP4 = 2;
+// The largest M it serves: gemm5 is a tuner candidate only up to here, and above it the dequant pass is small
+// against the GEMM.
+constexpr int WQ_GEMM_MAX_M = 512;
+
+// The one place that decides whether gemm_wq() runs a call and with which launch: a GEMM5 plan (nj n-tiles per wave,
+// the effective split of gemm5_ksplit(), the in-loop norm statistic, every epilogue in the reduce kernel), bit for
+// bit the plan gemm_plan() returns for tile 11 / 12 at the same split. tile / ksplit <= 0: the default plan (the tuner
+// is never asked, as for the quantised GEMVs) -- 4 n-tiles per wave unless that grid is under a third of the CUs, then
+// 2 (half the CUs at first: Llama-3-8B w1|w3, 112 wide tiles, then ran 448 narrow workgroups in 104 us at 256 rows
+// where one round of 224 wide ones takes 87 us); then the split that best fills one round of workgroups while each
+// split keeps at least 4 stages (below).
+inline GemmPlanResult gemm_wq_plan(int M, int N, int K, int mode, bool rms, int fmt, int ksplit, int tile, int cus) {
+  const auto fail = [](int rc) { return GemmPlanResult{rc, GemmPlan{}}; };
+  if (fmt != WQ_FP8 && fmt != WQ_MXFP4) return fail(-1);
+  if (mode != MODE_STORE && mode != MODE_RESIDUAL && mode != MODE_SWIGLU && mode != MODE_QKV) return fail(-1);
+  if (rms && mode == MODE_RESIDUAL) return fail(-5);  // the caller pre-scales x, as for gemm5
+  if (M <= 64 || M > WQ_GEMM_MAX_M) return fail(-1);  // (up to 64 rows: the quantised GEMVs)
+  if (N <= 0 || (N & 15) || (mode == MODE_SWIGLU && (N & 31))) return fail(-1);
+  if (K <= 0 || (K & (fmt == WQ_FP8 ? 63 : 127))) return fail(-1);
+  if (tile > 0 && tile != G5_TILE && tile != G5N_TILE) return fail(-1);
+  const int KS64 = K >> 6;
+  const int tiles_m = (M + (M <= 128 ? 127 : 255)) / (M <= 128 ? 128 : 256);
+  GemmPlan p{};
+  p.family = GEMM5;
+  p.nj = tile > 0 ? (tile == G5_TILE ? 4 : 2) : (3 * tiles_m * ((N + 255) / 256) < cus ? 2 : 4);
+  if (ksplit <= 0) {
+    // the two splits around one full round of workgroups: hi, the smallest that brings the grid to `cus`, and lo, the
+    // largest that stays within it. lo unless hi has fewer modelled stage-rounds (rounds of workgroups x stages per
+    // split): a grid just past one round pays a second round for a few stages less (the MP 8 w1|w3 shard at 96 rows:
+    // 5 splits, 280 workgroups, 39.3 us; 4 splits, 224 workgroups, 34.1 us -- profiles/README.md). Ties go to lo
+    // (w1|w3 at 512 rows: 1 split 148 us, 2 splits 167 us)
+    const int grid = tiles_m * ((N + 64 * p.nj - 1) / (64 * p.nj)), most = KS64 / 4 > 1 ? KS64 / 4 : 1;
+    const auto cost = [&](int s) { return (long long)((grid * s + cus - 1) / cus) * ((KS64 + s - 1) / s); };
+    int hi = (cus + grid - 1) / grid, lo = cus / grid > 1 ? cus / grid : 1;
+    hi = hi < most ? hi : most, lo = lo < most ? lo : most;
+    ksplit = cost(hi) < cost(lo) ? hi : lo;
+  }
+  p.ksplit = gemm5_ksplit(K, ksplit);
+  p.kc = (KS64 + p.ksplit - 1) / p.ksplit;
+  p.norm = rms ? NORM_INLOOP : NORM_NONE;
+  p.reduce = true;
+  return {0, p};
+}
+
 }  // namespace jla

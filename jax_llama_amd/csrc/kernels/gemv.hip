@@ -30,6 +30,7 @@
 #include "common.h"
 #include "launchers.h"
 #include "ring.h"
+#include "wq_cvt.h"
 
 namespace jla {
 
@@ -1134,16 +1135,7 @@ int linear_skinny(const void* x, int x_is_f32, const void* W, void* out, int M, 
 // + 0..7] in bytes 0-7 (the element order of the bf16 B fragment of k-step 2 kb) and the same at k + 32 in bytes 8-15
 // (k-step 2 kb + 1): one 16-byte load per lane is 1 KiB per wave, as the bf16 layout, and feeds two MFMAs.
 
-// 8 e4m3 bytes (two dwords) -> the 8 bf16 of one B fragment: four v_cvt_scalef32_pk_bf16_fp8 with scale 1.0 (every
-// e4m3 value is exact in bf16)
-JLA_DEV u32x4 fp8x8_to_bf16(unsigned lo, unsigned hi) {
-  u32x4 r;
-  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, false));
-  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(lo, 1.0f, true));
-  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, false));
-  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(hi, 1.0f, true));
-  return r;
-}
+// (fp8x8_to_bf16, the in-register e4m3 -> bf16 conversion: wq_cvt.h)
 
 // Dequantise a packed fp8 weight into the bf16 fragment-packed layout (common.h): thread = one lane of one 16 x 64
 // block; reads its 16 bytes, writes its 16 bytes of fragment 2 kb and of 2 kb + 1. q * scale in fp32 then RNE to bf16:
@@ -1378,17 +1370,7 @@ int linear_skinny_w8(const void* x, int x_is_f32, const void* W8, const float* s
 // are stored [N / 16][K / 128][16 rows][4]: one dword per (row, block), byte j the scale of k-step 4 kb + j; lane l
 // reads dword l & 15.
 
-// one dword of 8 e2m1 codes -> the 8 bf16 of one B fragment, times 2^(sbyte - 127): four v_cvt_scalef32_pk_bf16_fp4
-// whose fp32 scale operand is the e8m0 byte moved into the exponent field (a zero byte: 0.0, and code 0 converts to 0)
-JLA_DEV u32x4 fp4x8_to_bf16(unsigned q, unsigned sbyte) {
-  const float sc = __uint_as_float(sbyte << 23);
-  u32x4 r;
-  r[0] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 0));
-  r[1] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 1));
-  r[2] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 2));
-  r[3] = __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(q, sc, 3));
-  return r;
-}
+// (fp4x8_to_bf16, the in-register e2m1 -> bf16 conversion with the block scale as its operand: wq_cvt.h)
 
 // Dequantise a packed MXFP4 weight into the bf16 fragment-packed layout (common.h): thread = one lane of one 16 x 128
 // block; reads its 16 bytes and its row's scale dword, writes its 16 bytes of fragments 4 kb .. 4 kb + 3. The

@@ -120,6 +120,20 @@ int gemm_num_cus();                // CUs of the current device (gemm_plan's `cu
 void gemm_set_g4_default(int on);  // gemm_plan's `g4_default`: tile 0 runs gemm4 where it applies (on by default)
 void gemm_set_g4_group(int gm);    // tools: m-tiles per group of gemm4's launch order (0: the default, 4)
 void gemm5_set_diag(int d);        // tools only: gemm5 / gemm4 store ablations (wrong results)
+// The quantised-weight GEMM (gemm5q.h) for 64 < M <= WQ_GEMM_MAX_M: y = epilogue(x[M, K] @ W_deq[N, K]^T) straight
+// from the quantised bytes -- fmt WQ_FP8: Wq [N/16][K/64][64][16], S the fp32 row scales [N]; WQ_MXFP4: Wq
+// [N/16][K/128][64][16], S the e8m0 bytes [N/16][K/128][16][4]. Bit-identical to gemm() with tile 11 / 12 at the same
+// split on the dequantised copy. gemm_wq_plan() (gemm_plan.h) is every rule of a legal call (its codes; -3: ws too
+// small); tile / ksplit <= 0: its default plan. ws as gemm5: gemm_wq_ksplit() slabs (0: no plan).
+int gemm_wq(const bf16_t* x, const void* Wq, const void* S, int fmt, void* out, int M, int N, int K, int mode,
+            int accumulate, int out_f32, bf16_t* mirror, const QKVArgs* qkv, float* ws, size_t ws_floats, int ksplit,
+            int tile, float rms_eps, hipStream_t s);
+// the partial kernel alone (gemm_wq.hip): [ksplit][M][N] slabs into ws (+ [ksplit][M] sums of squares into ssq), ntw
+// n-tiles per wave, kc 64-deep stages per split
+int gemm5q_launch(const bf16_t* x, const void* Wq, const void* S, int fmt, float* ws, int M, int N, int K, float* ssq,
+                  int ntw, int ksplit, int kc, hipStream_t s);
+int gemm_wq_plan_check(int M, int N, int K, int mode, int rms, int fmt, int ksplit, int tile);
+int gemm_wq_ksplit(int M, int N, int K, int mode, int fmt, int ksplit, int tile);  // the plan's effective split
 // greedy lm_head: GEMM + first-max argmax epilogue (ws >= gemm_argmax_workspace_floats(M, N) floats)
 int gemm_argmax(const bf16_t* x, const void* W, float* ws, size_t ws_floats, int M, int N, int K, float rms_eps,
                 int32_t* idx, float* val, hipStream_t s, float* rms_ws = nullptr, size_t rms_ws_floats = 0);

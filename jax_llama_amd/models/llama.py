@@ -366,6 +366,31 @@ class LLaMAForCausalLM:
             return "mxfp4"
         return "fp8_e4m3" if any(getattr(lw.qkv, "fp8", False) for lw in self.layers) else "bf16"
 
+    QUANTIZED_GEMM_MODES = ("dequant", "direct")
+
+    def set_quantized_gemm(self, mode: str) -> "LLaMAForCausalLM":
+        """How the quantised projections run calls of more than 64 rows: ``"dequant"`` (the default) writes ``W_deq``
+        into a bf16 workspace and runs the tuned bf16 GEMM on it; ``"direct"`` streams the FP8 / MXFP4 bytes through
+        the quantised-weight GEMM (``ops._wq_direct``: 65 .. ``WQ_GEMM_MAX_M`` rows; calls it does not serve keep the
+        dequant path), bit-identical to the weight-streaming bf16 GEMM (tiles 11 / 12) on ``W_deq``. Runtime state:
+        not written to checkpoints. ``ValueError`` for an unknown mode, ``RuntimeError`` on a model that is not
+        quantised. Drops this model's cached decode engines (their graphs captured the other path)."""
+        if mode not in self.QUANTIZED_GEMM_MODES:
+            raise ValueError(f"set_quantized_gemm: unknown mode {mode!r} (one of {self.QUANTIZED_GEMM_MODES})")
+        if self.weight_format == "bf16":
+            raise RuntimeError("set_quantized_gemm: the model is not quantised (quantize_weights_ first)")
+        for lw in self.layers:
+            for name in ("qkv", "o", "gu", "down"):
+                getattr(lw, name).gemm_direct = mode == "direct"
+        self._quantized_gemm = mode
+        from ..runtime.engine import drop_engines
+        drop_engines(self)
+        return self
+
+    @property
+    def quantized_gemm(self) -> str:
+        return getattr(self, "_quantized_gemm", "dequant")
+
     def weight_bytes(self) -> int:
         n = self.wte.numel() * 2 + self.lm_head.nbytes()
         for lw in self.layers:

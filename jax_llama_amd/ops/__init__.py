@@ -310,6 +310,46 @@ def _w4_fast(e, x, w, mode) -> bool:
     return x.shape[0] > 0 and e.gemv_w4_plan_check(x.shape[0], w.n, w.k, mode, x.dtype != BF16)[0] == 0
 
 
+# The quantised-weight GEMM (csrc/kernels/gemm5q.h): with ``model.set_quantized_gemm("direct")`` the calls of 65 ..
+# ``WQ_GEMM_MAX_M`` rows on a quantised weight stream its bytes instead of dequantising first. ``WQ_GEMM_PLAN``:
+# ``(tile, ksplit)`` pins the plan (tile 11 / 12, any split) for tests and tools; None: gemm_wq_plan()'s default.
+WQ_GEMM_PLAN = None
+
+
+def _wq_plan():
+    return (0, 0) if WQ_GEMM_PLAN is None else (int(WQ_GEMM_PLAN[0]), int(WQ_GEMM_PLAN[1]))
+
+
+def _wq_fmt(e, w) -> int:
+    return e.WQ_MXFP4 if is_mxfp4(w) else e.WQ_FP8
+
+
+def _wq_direct(e, x, w, mode, rms_eps) -> bool:
+    """Whether this call on a quantised weight runs the quantised-weight GEMM: the weight is marked
+    (``set_quantized_gemm("direct")``) and gemm_wq_plan() of csrc/kernels/gemm_plan.h accepts the call."""
+    if not getattr(w, "gemm_direct", False) or not is_quantized(w):
+        return False
+    tile, ks = _wq_plan()
+    return e.gemm_wq_plan_check(x.shape[0], w.n, w.k, mode, _fused_rms(e, mode, rms_eps), _wq_fmt(e, w), ks, tile) == 0
+
+
+def _wq_input(e, x, w, mode, rms_eps):
+    """(bf16 A operand, fmt, tile, ksplit, slab workspace, rms_eps argument) of a ``_wq_direct`` call: x as the tiled
+    GEMM takes it, the workspace sized as ``_gemm_ws`` does for tiles 11 / 12."""
+    fused = _fused_rms(e, mode, rms_eps)
+    fmt = _wq_fmt(e, w)
+    tile, ks = _wq_plan()
+    m = x.shape[0]
+    eks = e.gemm_wq_ksplit(m, w.n, w.k, mode, fmt, ks, tile)
+    ws = workspace.get("gemm_ws", eks * m * (w.n + 1), torch.float32, x.device)
+    return _tiled_input(x, rms_eps, fused), fmt, tile, ks, ws, float(rms_eps) if fused else -1.0
+
+
+def _wq_gemm(e, x, w, out, mode, rms_eps, accumulate, mirror):
+    xb, fmt, tile, ks, ws, eps = _wq_input(e, x, w, mode, rms_eps)
+    e.gemm_wq(xb, w.qweight, w.scale, fmt, w.n, w.k, out, mode, bool(accumulate), mirror, ks, tile, ws, eps)
+
+
 def _gpu_linear(x, w, out, mode, rms_eps, accumulate, mirror=None, x_packed=None, pack_out=None):
     assert x.is_contiguous() and out.is_contiguous()
     assert x.shape[1] == w.k, (x.shape, w.k)
@@ -320,12 +360,16 @@ def _gpu_linear(x, w, out, mode, rms_eps, accumulate, mirror=None, x_packed=None
             e.linear_skinny_w4(x, w.qweight, w.scale, w.n, w.k, out, mode, -1.0 if rms_eps is None else float(rms_eps),
                                bool(accumulate), mirror, pack_out if mode != MODE_STORE else None)
             return
+        if _wq_direct(e, x, w, mode, rms_eps):
+            return _wq_gemm(e, x, w, out, mode, rms_eps, accumulate, mirror)
         w = bf16_weight(w)
     if is_fp8(w):
         if _w8_fast(e, x, w, mode):
             e.linear_skinny_w8(x, w.qweight, w.scale, w.n, w.k, out, mode, -1.0 if rms_eps is None else float(rms_eps),
                                bool(accumulate), mirror, pack_out if mode != MODE_STORE else None)
             return
+        if _wq_direct(e, x, w, mode, rms_eps):
+            return _wq_gemm(e, x, w, out, mode, rms_eps, accumulate, mirror)
         w = bf16_weight(w)
     if m > e.SKINNY_MAX_M:
         x_packed = pack_out = None
@@ -516,6 +560,16 @@ def rope_kv_write(qkv: torch.Tensor, table: torch.Tensor, positions: torch.Tenso
     return q
 
 
+def _wq_qkv(e, x, w, rms_eps, table, positions, k_cache, v_cache, slot0, seq_len, n_heads, n_kv_heads, head_dim):
+    """The qkv projection of a ``_wq_direct`` call: RoPE + KV-cache write in the reduce epilogue, as ``gemm_qkv``."""
+    xb, fmt, tile, ks, ws, eps = _wq_input(e, x, w, MODE_QKV, rms_eps)
+    q = torch.empty(x.shape[0], n_heads, head_dim, dtype=BF16, device=x.device)
+    e.gemm_wq_qkv(xb, w.qweight, w.scale, fmt, w.n, w.k, table, positions.reshape(-1).to(torch.int32), k_cache, v_cache,
+                  _slot_tensor(slot0, x.device), int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q, ks,
+                  tile, ws, eps)
+    return q
+
+
 def linear_qkv_rope(x: torch.Tensor, w, rms_eps: Optional[float], table: torch.Tensor, positions: torch.Tensor,
                     k_cache: torch.Tensor, v_cache: torch.Tensor, slot0, seq_len: int, n_heads: int,
                     n_kv_heads: int, head_dim: int, x_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -541,6 +595,9 @@ def linear_qkv_rope(x: torch.Tensor, w, rms_eps: Optional[float], table: torch.T
                             positions.reshape(-1).to(torch.int32), k_cache, v_cache, _slot_tensor(slot0, x.device),
                             int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q)
             return q
+        if _wq_direct(e, x, w, MODE_QKV, rms_eps):
+            return _wq_qkv(e, x, w, rms_eps, table, positions, k_cache, v_cache, slot0, seq_len, n_heads, n_kv_heads,
+                           head_dim)
         w = bf16_weight(w)
     if is_fp8(w):
         if _w8_fast(e, x, w, MODE_QKV):
@@ -549,6 +606,9 @@ def linear_qkv_rope(x: torch.Tensor, w, rms_eps: Optional[float], table: torch.T
                             positions.reshape(-1).to(torch.int32), k_cache, v_cache, _slot_tensor(slot0, x.device),
                             int(seq_len), int(n_heads), int(n_kv_heads), int(head_dim), q)
             return q
+        if _wq_direct(e, x, w, MODE_QKV, rms_eps):
+            return _wq_qkv(e, x, w, rms_eps, table, positions, k_cache, v_cache, slot0, seq_len, n_heads, n_kv_heads,
+                           head_dim)
         w = bf16_weight(w)
     if m > e.SKINNY_MAX_M:
         x_packed = None

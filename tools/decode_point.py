@@ -28,6 +28,9 @@ def main():
                     help="fp8 / mxfp4: the layer projections quantised to FP8 e4m3 / MXFP4 "
                     "(LLaMAForCausalLM.quantize_weights_); `bf16 fp8 mxfp4`: one model of each in this process, "
                     "measured alternately per point")
+    ap.add_argument("--quantized-gemm", nargs="+", choices=["dequant", "direct"], default=["dequant"],
+                    help="quantised weights above 64 rows: the dequant pass + bf16 GEMM, or the GEMM on the quantised "
+                    "bytes (LLaMAForCausalLM.set_quantized_gemm); both: every quantised point under each")
     ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"],
                     help="KV-cache format (LLaMAForCausalLM.set_kv_cache_format; fp8: e4m3 rows with power-of-two "
                     "scales); `bf16 fp8`: the same model with each, measured alternately per point")
@@ -60,8 +63,12 @@ def main():
                                  min_new_tokens=args.min_new_tokens)))
     for b in args.batch:
         for rep in range(args.reps):
-            for wf, kv, (pname, proc) in ((wf, kv, pr) for wf in models for kv in args.kv for pr in procs):
+            for wf, qg, kv, (pname, proc) in ((wf, qg, kv, pr) for wf in models
+                                              for qg in (args.quantized_gemm if wf != "bf16" else ["dequant"])
+                                              for kv in args.kv for pr in procs):
                 m = models[wf]
+                if wf != "bf16":
+                    m.set_quantized_gemm(qg)
                 m.set_kv_cache_format("fp8_e4m3" if kv == "fp8" else "bf16")
                 r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample,
                                    processors=proc)
@@ -69,6 +76,7 @@ def main():
                 r["model"] = args.model
                 r["mp"] = args.tp_proxy
                 r["weights"] = wf
+                r["quantized_gemm"] = qg
                 r["kv"] = kv
                 r["kv_cache_gb"] = round(m.config.num_hidden_layers * 2 * b * m.n_kv_heads *
                                          (args.prompt_len + args.gen_len) *
