@@ -64,7 +64,7 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
 def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int = 256, temperature: float = 0.8,
          top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1,
          repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-         quantized_gemm: str = "dequant"):
+         quantized_gemm: str = "dequant", top_k: int = 50):
     """Reference ``main`` (jax_example.py:33-40). ``num_beams > 1``: beam search (temperature is then taken as 0).
     Llama-3 (without beam search) stops on any of the tokenizer's ``stop_tokens`` (end of text, end of turn)."""
     generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache,
@@ -75,7 +75,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
     results = generator.generate_from_str(PROMPTS, max_gen_len=max_gen_len, temperature=temperature, top_p=top_p,
                                           num_beams=num_beams, repetition_penalty=repetition_penalty,
                                           no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens,
-                                          stop_token_ids=stops)
+                                          stop_token_ids=stops, top_k=top_k)
     if int(os.environ.get("RANK", "0")) == 0:
         for result in results:
             print(result)
@@ -85,7 +85,8 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
               weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1, repetition_penalty: float = 1.0,
-              no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, quantized_gemm: str = "dequant"):
+              no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, quantized_gemm: str = "dequant",
+              top_k: int = 50):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -101,7 +102,8 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
                          dtype=torch.int32)
     gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0 and num_beams == 1,
-                          temperature=temperature, top_p=top_p, pad_token_id=0, eos_token_id=-1, num_beams=num_beams,
+                          temperature=temperature, top_p=top_p, top_k=top_k, pad_token_id=0, eos_token_id=-1,
+                          num_beams=num_beams,
                           repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                           min_new_tokens=min_new_tokens)
     t0 = time.perf_counter()
@@ -122,6 +124,8 @@ if __name__ == "__main__":
     ap.add_argument("--max_gen_len", type=int, default=256)
     ap.add_argument("--temperature", type=float, default=0.8)
     ap.add_argument("--top_p", type=float, default=0.95)
+    ap.add_argument("--top_k", type=int, default=50,
+                    help="0: no top-k cut (pure nucleus sampling with --top_p < 1, pure temperature sampling at 1)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--batch", type=int, default=2)
@@ -146,9 +150,9 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.synthetic:
         synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
-                  a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm)
+                  a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
         main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
-             a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm)
+             a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k)

@@ -19,18 +19,11 @@
 // Ties: lower vocabulary index first (lax.top_k order).
 #include "common.h"
 #include "launchers.h"
+#include "sampler_keys.h"
 
 namespace jla {
 
 constexpr int TK_THREADS = 256, TK_E = 64, TK_CHUNK = TK_THREADS * TK_E;
-
-// -0.0 takes the key of +0.0: the two are equal logits (a tie goes to the lower index, like any other), not neighbours
-JLA_DEV uint32_t fkey(float f) {
-  uint32_t u = __float_as_uint(f);
-  if (u == 0x80000000u) u = 0u;
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-JLA_DEV float kfloat(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
 
 struct TkShared {
   uint32_t hist[256];
@@ -212,18 +205,6 @@ __global__ void __launch_bounds__(TK_THREADS)
     ov[slot] = valid ? kfloat(k) : -INFINITY;
     oi[slot] = valid ? idx_offset + e : 0x7fffffff;
   }, 16);
-}
-
-JLA_DEV uint4 philox4x32_10(uint4 ctr, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t lo0 = 0xD2511F53u * ctr.x, hi0 = __umulhi(0xD2511F53u, ctr.x);
-    const uint32_t lo1 = 0xCD9E8D57u * ctr.z, hi1 = __umulhi(0xCD9E8D57u, ctr.z);
-    ctr = make_uint4(hi1 ^ ctr.y ^ k.x, lo1, hi0 ^ ctr.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return ctr;
 }
 
 // mode 0: write the sorted top-K (out_v/out_i [B, K]); mode 1: sample one token per row into nxt[B].

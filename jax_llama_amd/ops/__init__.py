@@ -1047,6 +1047,35 @@ def topk_sample(logits: torch.Tensor, k: int, temperature: float, top_p: float, 
     return nxt
 
 
+NUCLEUS_MAX_V = 1 << 22  # nucleus_sample.hip: the row's integer masses (2^40 each at most) sum below 2^63
+
+
+def nucleus_sample(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: torch.Tensor,
+                   comm=None, return_kept: bool = False):
+    """temperature -> top-k (``top_k`` 0 or None: none) -> top-p -> categorical over the whole vocabulary, one launch
+    per call (csrc/kernels/nucleus_sample.hip; ``ref.nucleus_sample`` is the definition): threshold select by radix
+    descent, then Gumbel-max with noise keyed by the vocabulary index. Under TP the logits are all-gathered and every
+    rank runs the whole row: index-keyed noise makes the ranks agree without a second exchange. ``step`` is a device
+    int32[1], so the call is hipGraph-capturable. Returns int32 [B] (with ``return_kept``: and the survivor counts)."""
+    x = logits.float().contiguous()
+    if comm is not None and comm.size > 1:
+        x = comm.all_gather(x).permute(1, 0, 2).reshape(x.shape[0], -1).contiguous()
+    b, v = x.shape
+    if v > NUCLEUS_MAX_V:
+        raise ValueError(f"nucleus_sample: V = {v} above the kernel's limit {NUCLEUS_MAX_V}")
+    if not temperature > 0:
+        raise ValueError("nucleus_sample: temperature > 0")
+    top_p = 1.0 if top_p is None else float(top_p)
+    if not top_p > 0:
+        raise ValueError("nucleus_sample: top_p > 0")
+    if not _is_gpu(x):
+        return ref.nucleus_sample(x, top_k, temperature, top_p, seed, int(step.reshape(-1)[0]), return_kept)
+    nxt = torch.empty(b, dtype=torch.int32, device=x.device)
+    kept = torch.empty(b, dtype=torch.int32, device=x.device) if return_kept else None
+    ext().nucleus_sample(x, int(top_k or 0), float(temperature), top_p, int(seed) & ((1 << 63) - 1), step, nxt, kept)
+    return (nxt, kept) if return_kept else nxt
+
+
 # ---------------------------------------------------------------------------------- beam search
 BEAM_MAX = ref.BEAM_MAX
 

@@ -580,6 +580,58 @@ def topk_sample(logits: torch.Tensor, k: int, temperature: float, top_p: float, 
     return idx[torch.arange(b), torch.from_numpy(choice)].to(torch.int32)
 
 
+def nucleus_scores(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: int):
+    """The full-vocabulary sampler's definition in float64 (README "Full-vocabulary sampling"), row by row: a list of
+    ``(idx, score)``, the survivors' vocabulary indices (ascending) and their Gumbel scores ``l + g``.
+
+    Rank = position by raw logit descending, ties to the lower index. top-k keeps the first ``k`` ranks (``top_k`` 0 or
+    None: all). top-p (only when ``top_p < 1``): with ``l = x * fp32(1 / temperature)`` and ``e = exp(l - max l)``,
+    rank r survives iff the sum of ``e`` over the ranks before it is ``< top_p * Z``, ``Z`` = the sum over the top-k
+    survivors; rank 0 always survives. Noise: ``g_i = -log(-log(u_i))``, ``u_i = ((w >> 8) + 0.5) / 2^24``, ``w`` =
+    word ``i & 3`` of ``philox4x32_10((i >> 2, row, step, 1), seed)`` with ``i`` the vocabulary index. A row that is
+    all ``-inf`` counts as a row of equal logits."""
+    import numpy as np
+    x32 = logits.detach().float().cpu().numpy()
+    b, v = x32.shape
+    k = v if not top_k else min(int(top_k), v)
+    inv_t = float(np.float32(1.0 / float(temperature)))
+    key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    out = []
+    for r in range(b):
+        x = x32[r].astype(np.float64)
+        if np.all(np.isneginf(x)):
+            x = np.zeros(v)
+        order = np.argsort(-x, kind="stable")[:k]
+        l = x * inv_t
+        if top_p is not None and top_p < 1.0:
+            e = np.exp(l[order] - l[order[0]])
+            before = np.cumsum(e) - e
+            keep = before < float(top_p) * e.sum()
+            keep[0] = True
+            order = order[keep]
+        idx = np.sort(order)
+        grp, inv = np.unique(idx >> 2, return_inverse=True)
+        ctr = np.zeros((grp.size, 4), dtype=np.uint32)
+        ctr[:, 0], ctr[:, 1], ctr[:, 2], ctr[:, 3] = grp, r, np.uint32(step), 1
+        w = philox4x32_10(ctr, key)[inv, idx & 3]
+        u = ((w >> 8).astype(np.float64) + 0.5) / 16777216.0
+        out.append((idx, l[idx] - np.log(-np.log(u))))
+    return out
+
+
+def nucleus_sample(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: int,
+                   return_kept: bool = False):
+    """int32 ``[B]``: per row the argmax of ``nucleus_scores`` (ties to the lower index); with ``return_kept`` also
+    the number of survivors, int32 ``[B]``. The noise is keyed by vocabulary index with Philox counter word 3 = 1
+    (``topk_sample``: by rank, word 3 = 0), so one seed draws different tokens at ``top_k`` = 64 and 65."""
+    import numpy as np
+    rows = nucleus_scores(logits, top_k, temperature, top_p, seed, step)
+    tok = torch.tensor([int(idx[np.argmax(s)]) for idx, s in rows], dtype=torch.int32)
+    if return_kept:
+        return tok, torch.tensor([idx.size for idx, _ in rows], dtype=torch.int32)
+    return tok
+
+
 # ----------------------------------------------------------------------------------
 # Beam search (HF Flax ``_beam_search`` semantics; the README's "Beam search" section is the definition)
 # ----------------------------------------------------------------------------------

@@ -154,20 +154,38 @@ def _greedy(model, logits_local) -> torch.Tensor:
     return model.comm.argmax(val, idx, v_local)
 
 
+def _sampler_route(gc: GenerationConfig, v_local: int, tp: int, on_cpu: bool, has_step: bool) -> str:
+    """Which sampler ``_sample`` uses: "topk" (ops.topk_sample), "nucleus" (ops.nucleus_sample) or "torch"."""
+    v = v_local * tp
+    k = min(gc.top_k or 0, v)
+    if not (has_step and gc.temperature and gc.temperature > 0):
+        return "torch"
+    if 1 <= k <= ops.SAMPLER_MAX_K and (on_cpu or ops.ext().topk_chunks(v_local) * min(k, v_local) <= 4096):
+        return "topk"
+    return "nucleus" if v <= ops.NUCLEUS_MAX_V else "torch"
+
+
 def _sample(model, logits_local: torch.Tensor, gc: GenerationConfig, gen: Optional[torch.Generator],
             step: Optional[torch.Tensor] = None):
     """temperature -> top-k -> top-p -> categorical (Gumbel-max), exact under vocab sharding.
 
     top_k in [1, 64] (HF default 50): the on-device sampler (ops.topk_sample: radix-select top-k
     kernels + Philox Gumbel-max keyed by (seed, step)), graph-capturable and identical on CPU.
-    Otherwise (top_k = 0 / > 64): torch sort path."""
+    top_k = 0 / None (pure nucleus or pure temperature sampling), top_k > 64, or more top-k candidates than the merge
+    takes: the full-vocabulary sampler (ops.nucleus_sample: one launch per step, threshold select + Gumbel-max keyed by
+    the vocabulary index; under TP on the gathered logits), graph-capturable and identical on CPU as well.
+    The torch sort path is left for what neither takes: no device ``step`` (a caller outside the decode loop), or a
+    vocabulary above ops.NUCLEUS_MAX_V."""
     comm = model.comm
     v_local = logits_local.shape[1]
     k = min(gc.top_k or 0, v_local * comm.size)
-    if step is not None and 1 <= k <= ops.SAMPLER_MAX_K and gc.temperature and gc.temperature > 0:
-        if logits_local.device.type == "cpu" or ops.ext().topk_chunks(v_local) * min(k, v_local) <= 4096:
-            return ops.topk_sample(logits_local.float().contiguous(), k, gc.temperature, gc.top_p,
-                                   gc.seed, step, comm if comm.size > 1 else None)
+    route = _sampler_route(gc, v_local, comm.size, logits_local.device.type == "cpu", step is not None)
+    if route == "topk":
+        return ops.topk_sample(logits_local.float().contiguous(), k, gc.temperature, gc.top_p,
+                               gc.seed, step, comm if comm.size > 1 else None)
+    if route == "nucleus":
+        return ops.nucleus_sample(logits_local, gc.top_k or 0, gc.temperature, gc.top_p, gc.seed, step,
+                                  comm if comm.size > 1 else None)
     x = logits_local.float()
     if gc.temperature is not None and gc.temperature != 1.0:
         x = x / gc.temperature
@@ -421,13 +439,14 @@ class DecodeEngine:
         if gc.do_sample:
             self._gen = torch.Generator(device=self.device)
             self._gen.manual_seed(int(gc.seed))
+            # The on-device samplers (ops.topk_sample, ops.nucleus_sample) draw from their own Philox streams keyed by
+            # (seed, step) and touch no torch RNG. Only the torch path that is left (_sampler_route) under graph
+            # capture needs the device's default generator (graph-safe philox offsets): seed it for this call and
+            # give the caller's RNG state back afterwards.
             if self.use_graph:
-                # The on-device sampler (ops.topk_sample, top_k <= 64) draws from its own Philox stream keyed by
-                # (seed, step) and touches no torch RNG. The torch fallback (top_k = 0 or > 64) under graph capture
-                # needs the device's default generator (graph-safe philox offsets): seed it for this call and give
-                # the caller's RNG state back afterwards.
                 self._gen = None
-                if self.device.type == "cuda":
+                if self.device.type == "cuda" and _sampler_route(
+                        gc, self.model.vocab_local, self.model.comm.size, False, True) == "torch":
                     rng_saved = torch.cuda.get_rng_state(self.device)
                     torch.cuda.manual_seed(int(gc.seed))
         try:

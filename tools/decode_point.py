@@ -22,6 +22,9 @@ def main():
     ap.add_argument("--prompt-len", type=int, default=128)
     ap.add_argument("--gen-len", type=int, default=256)
     ap.add_argument("--sample", action="store_true")
+    ap.add_argument("--top-k", type=int, default=50, help="with --sample: 0 = no top-k cut (the full-vocabulary sampler)")
+    ap.add_argument("--top-p", type=float, default=0.95)
+    ap.add_argument("--temperature", type=float, default=0.8)
     ap.add_argument("--tp-proxy", type=int, default=1, help="> 1: ONE rank of that MP degree on this GPU "
                     "(parallel/comm.py TPRankProxyComm; bench.py tp_rank_proxy)")
     ap.add_argument("--weights", nargs="+", choices=["bf16", "fp8", "mxfp4"], default=["bf16"],
@@ -71,7 +74,9 @@ def main():
                     m.set_quantized_gemm(qg)
                 m.set_kv_cache_format("fp8_e4m3" if kv == "fp8" else "bf16")
                 r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample,
-                                   processors=proc)
+                                   processors=proc,
+                                   sampler=dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature))
+                r["top_k"], r["top_p"], r["temperature"] = args.top_k, args.top_p, args.temperature
                 r["processors"] = pname
                 r["model"] = args.model
                 r["mp"] = args.tp_proxy
