@@ -783,6 +783,39 @@ void attn_decode_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor
      "attn_decode_q8");
 }
 
+// S > 1 straight on the fp8 bytes (kernels/attn_prefill.hip, the Q8 instantiations). True: launched. False: the shape
+// resolves to the v1 kernel, which reads bf16 rows only -- nothing was launched and the caller dequantises.
+bool attn_prefill_q8(Tensor q, Tensor kq, Tensor ks, Tensor vq, Tensor vs, Tensor slot, Tensor kv_start,
+                     c10::optional<Tensor> key_mask, Tensor out) {
+  for (auto* t : {&q, &slot, &kv_start, &out}) check_gpu(*t, "attn_prefill_q8 arg");
+  check(q.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16 && q.dim() == 4,
+        "attn_prefill_q8: q bf16 [B, S, H, Dh]");
+  const int64_t b = q.size(0), s = q.size(1), h = q.size(2), dh = q.size(3);
+  check(dh == jla::ATTN_DH, "attn_prefill_q8: Dh == 128");
+  check(kq.dim() == 4, "attn_prefill_q8: q bytes must be uint8 [B, Hkv, T, 128]");
+  const int64_t hkv = kq.size(1), T = kq.size(2);
+  check_kv8(kq, ks, vq, vs, b, hkv, "attn_prefill_q8 cache");
+  check(h % hkv == 0, "H must be a multiple of Hkv");
+  check(slot.scalar_type() == torch::kInt32 && slot.numel() >= 1 && kv_start.scalar_type() == torch::kInt32 &&
+            kv_start.numel() == b,
+        "slot/kv_start");
+  check(out.numel() == q.numel(), "attention out shape");
+  check(T <= INT32_MAX && b * s * h <= INT32_MAX, "attn_prefill_q8: sizes");
+  if (key_mask.has_value()) {
+    check_gpu(*key_mask, "key_mask");
+    check(key_mask->scalar_type() == torch::kUInt8 && key_mask->dim() == 2 && key_mask->size(0) == b,
+          "key_mask must be uint8 [B, L]");
+  }
+  const uint8_t* km = key_mask.has_value() ? ptr<uint8_t>(*key_mask) : nullptr;
+  const int ml = key_mask.has_value() ? key_mask->size(1) : 0;
+  const int r = jla::attn_prefill_q8(cbf(q), ptr<uint8_t>(kq), ptr<float>(ks), ptr<uint8_t>(vq), ptr<float>(vs),
+                                     ptr<int32_t>(slot), ptr<int32_t>(kv_start), km, ml, bf(out), b, s, h, hkv, dh, T,
+                                     stream());
+  if (r == 1) return false;
+  rc(r, "attn_prefill_q8");
+  return true;
+}
+
 void argmax(Tensor logits, Tensor idx, Tensor val) {
   check_gpu(logits, "logits");
   check_gpu(idx, "idx");
@@ -1465,6 +1498,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"));
   m.def("attn_set_q8_splits", [](int64_t n) { jla::attn_set_q8_splits((int)n); },
         "key splits per pair of the fp8-cache decode attention: 0 by shape, 1 never, n > 1 pinned (tests, A/B)");
+  m.def("attn_prefill_q8", &attn_prefill_q8, py::arg("q"), py::arg("kq"), py::arg("ks"), py::arg("vq"), py::arg("vs"),
+        py::arg("slot"), py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"));
+  // (rc, why, direct) of S > 1 on an fp8 cache under the current knobs (kernels/attn_plan.h attn_prefill_q8_plan);
+  // n_keys: the rows the dequant pass would convert (slot0 + S with a host slot, T with a device-side one)
+  m.def("attn_prefill_q8_plan_check", [](int64_t b, int64_t h, int64_t hkv, int64_t s, int64_t n_keys) {
+    const jla::AttnPrefillQ8PlanResult r =
+        jla::attn_prefill_q8_plan(jla::attn_knobs(), (int)b, (int)h, (int)hkv, (int)s, (int)n_keys);
+    return py::make_tuple(r.rc, r.why, r.direct);
+  }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("s"), py::arg("n_keys"));
+  m.def("attn_set_q8_prefill", [](int64_t mode) { jla::attn_set_q8_prefill((int)mode); },
+        "S > 1 on an fp8 cache: -1 by attn_prefill_q8_plan, 0 always kv8_dequant + attn_prefill, 1 always direct");
   // (n_act, [(key_begin, key_end) per split]) of the valid keys [lo, hi) at kpg key rows per lane group: the geometry
   // function the 8-wave kernel calls (kernels/attn_plan.h attn_q8_split_range), on the host
   m.def("attn_q8_split_ranges", [](int64_t lo, int64_t hi, int64_t kpg, int64_t nsplit) {

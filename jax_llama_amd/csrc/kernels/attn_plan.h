@@ -31,6 +31,7 @@ struct AttnKnobs {
   bool v2_kpg4 = false;     // impl 4: v2's (KPG 4, 2 slots) ring at rep <= 4 for every size, not only from 16384 pairs
   int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8; 0 = by shape
   int q8_splits = 0;        // ... its key splits per pair: 0 = by shape, 1 = never, n > 1 pinned (clamped to the chunks of t_cap)
+  int q8_prefill = -1;      // S > 1 on the fp8 KV cache (attn_prefill_q8_plan): -1 = by shape, 0 = always dequantise, 1 = always direct
 };
 
 enum AttnKernel { ATTN_V2 = 2, ATTN_V3, ATTN_V4, ATTN_V5, ATTN_V6 };
@@ -276,6 +277,51 @@ inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, in
     p.tickets = pairs;
   }
   return {0, "", p};
+}
+
+// ---- S > 1 on the FP8 KV cache: the flash prefill kernel straight on the fp8 bytes (attn_prefill.hip, the Q8
+// instantiations of attn_prefill_v2_kernel: the tiles are converted while they are staged), or kv8_dequant into a bf16
+// scratch and the bf16 kernel on that. The two routes write the same bits, so the rule below changes no output.
+constexpr int ATTN_PREFILL_UNPIPED_MAX_S = 256;  // attn_prefill's default dispatch: the unpipelined loop up to here
+constexpr int ATTN_PREFILL_Q8_DIRECT_MIN_KEYS = 32768;  // S > 256: direct from this many rows to dequantise; see the rule
+struct AttnPrefillQ8PlanResult {
+  int rc;           // 0 legal; -1 not
+  const char* why;  // the rule that refused the call, or the one that chose the route
+  bool direct;      // one launch on the fp8 bytes; false: kv8_dequant + attn_prefill on the scratch
+};
+// n_keys: the rows the dequant pass would convert -- slot0 + S with the slot on the host, the cache length T with a
+// device-side slot.
+inline AttnPrefillQ8PlanResult attn_prefill_q8_plan(const AttnKnobs& k, int B, int H, int Hkv, int S, int n_keys) {
+  if (H < 1 || Hkv < 1 || H % Hkv) return {-1, "GQA: H a positive multiple of Hkv", false};
+  if (B < 0 || S < 1 || n_keys < 0) return {-1, "sizes: B >= 0, S >= 1, n_keys >= 0", false};
+  const int rep = H / Hkv;
+  // the GQA-shared kernel serves these ratios; every other one runs the v1 kernel, which has no fp8 staging
+  if (rep > 8 || (rep & (rep - 1))) return {0, "query heads per kv head other than 1, 2, 4, 8: the v1 kernel, dequantised", false};
+  if (k.q8_prefill == 0) return {0, "pinned: always dequantise", false};
+  if (k.q8_prefill == 1) return {0, "pinned: always direct", true};
+  // Direct where the launch runs the unpipelined loop (S <= 256: its register-staged tile simply halves), and where the
+  // dequant pass would convert a long cache for a short launch (n_keys >= 32768 and >= 16 S); dequantised otherwise.
+  // Records (profiles/kv8_attn_prefill_ab.jsonl, the README's "FP8 KV cache" prefill table; one MI355X, interleaved in
+  // one process, medians of 7 rounds, us: bf16 cache / dequant + bf16 kernel / direct), Llama-3-8B (H 32, Hkv 8):
+  //   n_keys = slot0 + S (host slot)  B = 1 S = 2048: 83.3 / 98.7 / 105.4    B = 16 S = 2048: 744 / 808 / 845
+  //     B = 1 S = 8192: 596 / 629 / 637 (the rounds overlap)    S = 512 at slot 7680: 224 / 243 / 299
+  //     B = 8 S = 128 at 8064: 293 / 383 / 278    B = 32 S = 8 at 4096: 182 / 326 / 168
+  //     Llama-3-70B MP 8 (H 8, Hkv 1) B = 1 S = 2048: 73.4 / 84.6 / 96.6
+  //   n_keys = T = 8192 (device-side slot)  S = 512 at 7680: 211 / 225 / 283, at slot 0: 21.9 / 33.0 / 30.6
+  //     B = 1 S = 2048 at 0: 68.7 / 80.5 / 85.7 (overlap)    B = 16 S = 2048 at 0: 750 / 905 / 828
+  //     B = 8 S = 128 at 8064: 277 / 363 / 262    B = 32 S = 8 at 4096: 166 / 439 / 154
+  //   n_keys = T = 32768 (device-side slot)  B = 1 S = 2048 at 0: 66.8 / 99.4 / 84.2, at 30720: 1145 / 1188 / 1133
+  //     B = 4 S = 512 at 0: 27.4 / 168.6 / 33.6, at 32256: 1335 / 1465 / 1299
+  // The unpipelined direct launch beats the two launches by 1.4-2.9x. The pipelined direct form (8 waves, half a tile
+  // of MFMAs for each staged load to land, the conversions in every workgroup) loses 1-23 % where the pass converts
+  // only the rows the launch reads. At n_keys = 8192 the records disagree -- the same (B, S, n_keys) wins 7 % at slot
+  // 0 and loses 26 % at the end of the cache, and the host cannot tell which it is -- so those launches stay
+  // dequantised; at n_keys = 32768 direct wins at both ends of the cache (4-80 %). Between 8192 and 32768 keys, and
+  // n_keys >= 32768 with S > n_keys / 16, are not measured and stay dequantised.
+  if (S <= ATTN_PREFILL_UNPIPED_MAX_S) return {0, "S <= 256 (the unpipelined loop): direct", true};
+  if (n_keys >= ATTN_PREFILL_Q8_DIRECT_MIN_KEYS && n_keys / 16 >= S)
+    return {0, "S > 256 with n_keys >= 32768 and >= 16 S (a long dequant pass): direct", true};
+  return {0, "S > 256 (a pipelined loop): dequantised", false};
 }
 
 }  // namespace jla

@@ -17,6 +17,7 @@
 
 #include "common.h"
 #include "launchers.h"
+#include "wq_cvt.h"
 
 namespace jla {
 
@@ -195,6 +196,11 @@ __global__ void __launch_bounds__(256)
 // the barrier that ends tile t). Causal: the workgroup stops at its last query's slot; a wave whose
 // queries all precede a tile skips its MFMAs; only tiles that cross the diagonal, kv_start or T are
 // masked element-wise. Each workgroup runs a heavy and a light query block (causal balance).
+// Where S is no multiple of 32 the last wave's lanes past S are clamped copies of the last query that are never stored,
+// but they keep their own slots slot0 + pos >= slot0 + S, so they score up to 31 cache rows past slot0 + S (below T), and
+// their tile maximum can take the wave-uniform lazy-rescale branch below. The real lanes' output then depends, by a
+// rounding of the running maximum, on what those rows hold: with S % 32 != 0 the bits are a function of those rows
+// too, not only of the rows the queries see (both cache formats alike; tests/test_kv8_prefill_gpu.py measures it).
 constexpr int FA_KT = 64;  // keys per tile
 
 // byte offset of 16-byte chunk ch (0..15) of row `row` in a [rows][128 bf16] image whose XOR swizzle
@@ -229,9 +235,28 @@ JLA_DEV u32x2 ld_tr(const char* lds, int off) {
 // the first V read of every tile, i.e. waited for the DMA of the NEXT tiles it had just issued), and branch-free, with
 // the next tile's 16 scores MFMAs spread over the 4 key steps (4 per step, fenced by sched_barrier) beside the exps and
 // PV MFMAs instead of sunk into one serial read -> wait -> MFMA chain at the end of the tile.
-template <int NW, int PIPE>
+//
+// Q8: the FP8 KV cache (kv8.hip) read in place. kc / vc are then the e4m3 bytes [B, Hkv, T, 128] and ksc / vsc the fp32
+// power-of-two row scales [B, Hkv, T]; only the staging differs. A thread's unit is the 8 bytes that become the 16-byte
+// chunk (row, ch) of the LDS image: one 8-byte load plus the row's scale (the 16 lanes of a row read one address), four
+// v_cvt_scalef32_pk_bf16_fp8 with the scale as the instruction's scale operand, one ds_write_b128 at fa_off(row, ch).
+// The images hold exactly q * scale in bf16 -- kv8_dequant's bits -- and everything after the staging is the bf16
+// kernel's code, so every impl gives the bits it gives on the dequantised rows. A 64-key tile is 8 + 8 KiB of bytes
+// and 64 + 64 scales from memory instead of 16 + 16 KiB. Rows no query sees (before kv_start, past the diagonal,
+// unwritten slots whose scale is 0.0, an exponent field the conversion reads as 2^-127) only have to stay finite: their
+// p is exactly 0.
+// PIPE with Q8 (built for the 8-wave PIPE 2 loop only; see launch_prefill_impl): LDS-DMA cannot convert on the way, so
+// K(i+2) / V(i+1) are register-staged through ONE unit in flight -- the 16 bytes of two neighbouring chunks of a row
+// and the row's scale, 5 registers: the tile's MFMAs leave no room for a whole staged tile. K(i+2)'s unit is loaded
+// where the DMAs are issued, converted and written to its free ring slot after key step 1, where V(i+1)'s unit is
+// loaded; that one is written before the barrier that ends the tile. The compiler's counted vmcnt waits sit at the
+// conversions, so each load has half a tile of MFMAs to land. The 2 + 2-slot bf16 rings and the one barrier per tile
+// stay. (Built instead of a DMA of the raw bytes into an fp8 LDS slot with an LDS -> LDS conversion: that form takes
+// 16 KiB more LDS per workgroup, 160 KiB for the two resident workgroups -- all a CU has.)
+template <int NW, int PIPE, bool Q8 = false>
 __global__ void __launch_bounds__(NW * 64, 2)
     attn_prefill_v2_kernel(const bf16_t* __restrict__ q, const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc,
+                           const float* __restrict__ ksc, const float* __restrict__ vsc,
                            const int32_t* __restrict__ slot_ptr, const int32_t* __restrict__ kv_start,
                            const uint8_t* __restrict__ key_mask, int mask_len, bf16_t* __restrict__ out, int S, int H,
                            int Hkv, int T, float scale_log2, int npb, int hgroups, int n_qb, int split) {
@@ -305,12 +330,44 @@ __global__ void __launch_bounds__(NW * 64, 2)
   const int last_key = min(slot0 + wg_last_pos, T - 1);
   const int t_begin = (lo / FA_KT) * FA_KT;
   const int wave_last_slot = slot0 + min(p0 + QW - 1, S - 1);
-  const bf16_t* kb = kc + ((size_t)b * Hkv + kvh) * T * AP_DH;
-  const bf16_t* vb = vc + ((size_t)b * Hkv + kvh) * T * AP_DH;
+  const size_t pair_row = ((size_t)b * Hkv + kvh) * T;
+  const bf16_t* kb = kc + pair_row * AP_DH;
+  const bf16_t* vb = vc + pair_row * AP_DH;
+  // Q8: the pair's e4m3 rows (128 bytes each) and row scales
+  const uint8_t* kb8 = reinterpret_cast<const uint8_t*>(kc) + pair_row * AP_DH;
+  const uint8_t* vb8 = reinterpret_cast<const uint8_t*>(vc) + pair_row * AP_DH;
+  const float* ksb = ksc + pair_row;
+  const float* vsb = vsc + pair_row;
+  // Q8 staging: the 8 bytes and the row scale of this thread's chunks of one tile, then convert + ds_write_b128
+  auto q8_fetch = [&](const uint8_t* src, const float* ssrc, int t0, u32x2 (&qr)[CH_PER_T], float (&sr)[CH_PER_T]) {
+#pragma unroll
+    for (int i = 0; i < CH_PER_T; ++i) {
+      const int c = tid + NT * i, row = c >> 4, ch = c & 15;
+      const int j = min(t0 + row, T - 1);
+      qr[i] = *reinterpret_cast<const u32x2*>(src + (size_t)j * AP_DH + 8 * ch);
+      sr[i] = ssrc[j];
+    }
+  };
+  auto q8_commit = [&](char* dst, const u32x2 (&qr)[CH_PER_T], const float (&sr)[CH_PER_T]) {
+#pragma unroll
+    for (int i = 0; i < CH_PER_T; ++i) {
+      const int c = tid + NT * i, row = c >> 4, ch = c & 15;
+      *reinterpret_cast<u32x4*>(dst + fa_off(row, ch)) = fp8x8_to_bf16(qr[i][0], qr[i][1], sr[i]);
+    }
+  };
+  u32x2 rk[CH_PER_T], rv[CH_PER_T];
+  float rks[CH_PER_T], rvs[CH_PER_T];
+  u32x4 ru;   // PIPE: the unit in flight
+  float rus;
 
   // staging: thread handles chunks c = tid + NT * i (row = c >> 4, ch = c & 15) of each tile
   u32x4 sk[CH_PER_T], sv[CH_PER_T];
   auto load_tile = [&](int t0) {
+    if constexpr (Q8) {
+      q8_fetch(kb8, ksb, t0, rk, rks);
+      q8_fetch(vb8, vsb, t0, rv, rvs);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < CH_PER_T; ++i) {
       const int c = tid + NT * i, row = c >> 4, ch = c & 15;
@@ -320,6 +377,11 @@ __global__ void __launch_bounds__(NW * 64, 2)
     }
   };
   auto store_tile = [&]() {
+    if constexpr (Q8) {
+      q8_commit(Ks, rk, rks);
+      q8_commit(Vs, rv, rvs);
+      return;
+    }
 #pragma unroll
     for (int i = 0; i < CH_PER_T; ++i) {
       const int c = tid + NT * i, row = c >> 4, ch = c & 15;
@@ -361,12 +423,25 @@ __global__ void __launch_bounds__(NW * 64, 2)
     const int n_t = t_begin <= last_key ? (last_key - t_begin) / FA_KT + 1 : 0;
     const int qfirst = slot0 + p0, qslot = qfirst + col;
     f32x16 st[2];
-    if (n_t > 0) {
-      dma(kb, t_begin, Kr(0));
-      dma(vb, t_begin, Vr(0));
+    if constexpr (Q8) {
+      if (n_t > 0) {
+        q8_fetch(kb8, ksb, t_begin, rk, rks);
+        q8_fetch(vb8, vsb, t_begin, rv, rvs);
+        q8_commit(Kr(0), rk, rks);
+        q8_commit(Vr(0), rv, rvs);
+      }
+      if (n_t > 1) {
+        q8_fetch(kb8, ksb, t_begin + FA_KT, rk, rks);
+        q8_commit(Kr(1), rk, rks);
+      }
+    } else {
+      if (n_t > 0) {
+        dma(kb, t_begin, Kr(0));
+        dma(vb, t_begin, Vr(0));
+      }
+      if (n_t > 1) dma(kb, t_begin + FA_KT, Kr(1));
+      wait_vmcnt<0>();
     }
-    if (n_t > 1) dma(kb, t_begin + FA_KT, Kr(1));
-    wait_vmcnt<0>();
     __syncthreads();
     if (n_t > 0 && t_begin <= wave_last_slot) scores(Kr(0), st);
     // the first iteration's DMA of K(2) lands in K(0)'s slot: every wave must be done reading it
@@ -375,8 +450,35 @@ __global__ void __launch_bounds__(NW * 64, 2)
       const int t0 = t_begin + it * FA_KT, cur = it & 1;
       const bool has1 = it + 1 < n_t, has2 = it + 2 < n_t;
       // K(i+2) into K(i)'s slot and V(i+1) into V(i-1)'s: both last read before the previous barrier
-      if (has2) dma(kb, t0 + 2 * FA_KT, Kr(cur));
-      if (has1) dma(vb, t0 + FA_KT, Vr(cur ^ 1));
+      // Q8 (8 waves: 512 threads x 16 raw bytes = one 64-row tile): the same tiles through ONE staging unit per thread,
+      // the 16 bytes of two neighbouring chunks of row tid / 8 and the row's scale (5 registers, one load each). K(i+2)'s
+      // unit is loaded here; after key step 1 it is converted and written to Kr(cur) and V(i+1)'s unit is loaded
+      // (q8_mid), which is written to Vr(cur ^ 1) before the closing barrier. Guarded by has2 / has1 exactly as the
+      // DMAs are, so a slot is written only where the DMA would write it and the barriers above cover the same cases.
+      static_assert(!Q8 || NW == 8, "fp8 staging of the pipelined loop: 8 waves (one 16-byte unit per thread and tile)");
+      auto q8_fetch_u = [&](const uint8_t* src, const float* ssrc, int tile0) {
+        const int j = min(tile0 + (tid >> 3), T - 1);
+        ru = *reinterpret_cast<const u32x4*>(src + (size_t)j * AP_DH + 16 * (tid & 7));
+        rus = ssrc[j];
+      };
+      auto q8_commit_u = [&](char* dst) {
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+          *reinterpret_cast<u32x4*>(dst + fa_off(tid >> 3, 2 * (tid & 7) + k)) =
+              fp8x8_to_bf16(ru[2 * k], ru[2 * k + 1], rus);
+      };
+      auto q8_mid = [&]() {
+        if constexpr (Q8) {
+          if (has2) q8_commit_u(Kr(cur));
+          if (has1) q8_fetch_u(vb8, vsb, t0 + FA_KT);
+        }
+      };
+      if constexpr (Q8) {
+        if (has2) q8_fetch_u(kb8, ksb, t0 + 2 * FA_KT);
+      } else {
+        if (has2) dma(kb, t0 + 2 * FA_KT, Kr(cur));
+        if (has1) dma(vb, t0 + FA_KT, Vr(cur ^ 1));
+      }
       if (t0 <= wave_last_slot) {  // wave-uniform; every later tile is inactive too
         // masking (wave-uniform branch: only tiles crossing kv_start, the diagonal, T, or a key mask)
         const bool full = !mrow && t0 >= lo && t0 + FA_KT - 1 <= qfirst && t0 + FA_KT - 1 < T;
@@ -455,6 +557,7 @@ __global__ void __launch_bounds__(NW * 64, 2)
               const u32x4 vf = {lo4[0], lo4[1], hi4[0], hi4[1]};
               o[0][dt] = mfma32(vf, pf, o[0][dt]);
             }
+            if (s == 1) q8_mid();
           }
           rs += __shfl_xor(rs, 32, 64);
           l_run[0] += rs;
@@ -471,8 +574,14 @@ __global__ void __launch_bounds__(NW * 64, 2)
           body(std::true_type{});
         else
           body(std::false_type{});
+      } else {
+        q8_mid();
       }
-      wait_vmcnt<0>();
+      if constexpr (Q8) {
+        if (has1) q8_commit_u(Vr(cur ^ 1));
+      } else {
+        wait_vmcnt<0>();
+      }
       __syncthreads();
     }
   } else {
@@ -594,8 +703,9 @@ __global__ void __launch_bounds__(NW * 64, 2)
 
 // v2 launch with NW waves per workgroup: NW / rep position blocks (rep < NW) or NW of the rep q heads (rep >= NW) share
 // each K/V tile the workgroup stages; `paired_only`: always the (heavy, light) pair per workgroup
-template <int NW, int PIPE>
-static void launch_prefill_v2(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot,
+template <int NW, int PIPE, bool Q8>
+static void launch_prefill_v2(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const float* ksc, const float* vsc,
+                              const int32_t* slot,
                               const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S,
                               int H, int Hkv, int T, int rep, bool paired_only, hipStream_t s) {
   const int npb = rep >= NW ? 1 : NW / rep;    // position blocks per workgroup
@@ -608,12 +718,13 @@ static void launch_prefill_v2(const bf16_t* q, const bf16_t* kc, const bf16_t* v
   // holds two resident workgroups instead of one
   const bool split = !paired_only && pairs < 2 * 256;
   if (split) {
-    attn_prefill_v2_kernel<NW, PIPE><<<dim3(2 * pairs, 1, 1), NW * 64, 0, s>>>(
-        q, kc, vc, slot, kv_start, key_mask, mask_len, out, S, H, Hkv, T, sl2, npb, hgroups, n_qb, 1);
+    attn_prefill_v2_kernel<NW, PIPE, Q8><<<dim3(2 * pairs, 1, 1), NW * 64, 0, s>>>(
+        q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, S, H, Hkv, T, sl2, npb, hgroups, n_qb, 1);
   } else {
     dim3 grid2((n_qb + 1) / 2, Hkv * hgroups, B);  // a (heavy, light) pair of query blocks per workgroup
-    attn_prefill_v2_kernel<NW, PIPE><<<grid2, NW * 64, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, S,
-                                                                H, Hkv, T, sl2, npb, hgroups, n_qb, 0);
+    attn_prefill_v2_kernel<NW, PIPE, Q8><<<grid2, NW * 64, 0, s>>>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask,
+                                                                    mask_len, out, S, H, Hkv, T, sl2, npb, hgroups,
+                                                                    n_qb, 0);
   }
 }
 
@@ -623,11 +734,9 @@ static void launch_prefill_v2(const bf16_t* q, const bf16_t* kc, const bf16_t* v
 static int g_attn_prefill_impl = 2;
 void attn_prefill_set_impl(int impl) { g_attn_prefill_impl = impl; }
 
-int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
-                 const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,
-                 hipStream_t s) {
-  if (B <= 0 || S <= 0) return 0;
-  if (Dh != AP_DH || H % Hkv) return -1;
+// The launch a shape resolves to under attn_prefill_set_impl: a v2 impl (7 / 8 / 9 / 13), or 1, the v1 kernel. One
+// function for the bf16 launch and the fp8-cache launch, so both run the same impl at the same shape.
+static int prefill_resolve_impl(int B, int S, int H, int Hkv) {
   const int rep = H / Hkv;
   const bool pow2rep = rep == 1 || rep == 2 || rep == 4 || rep == 8;
   int impl = g_attn_prefill_impl;
@@ -639,7 +748,7 @@ int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int3
   // The 8-wave launch is PIPE 2 (impl 13) since round 4: bit-identical to impl 9, +1-5 % on the 8-wave shapes
   // (profiles/r4_attn_prefill_asm_dma_ab.jsonl).
   if (impl == 2 && pow2rep) {
-    if (S <= 256) {
+    if (S <= ATTN_PREFILL_UNPIPED_MAX_S) {
       impl = 8;
     } else {
       const int npb8 = rep >= 8 ? 1 : 8 / rep;
@@ -652,21 +761,78 @@ int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int3
     }
   }
   const int nw_impl = impl == 9 || impl == 13 ? 8 : 4;
-  if ((impl == 7 || impl == 8 || impl == 9 || impl == 13) && (rep % nw_impl == 0 || nw_impl % rep == 0)) {
-    if (impl == 7)
-      launch_prefill_v2<4, 1>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep, false, s);
-    else if (impl == 8)
-      launch_prefill_v2<4, 0>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep, false, s);
-    else if (impl == 9)
-      launch_prefill_v2<8, 1>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep, true, s);
+  if ((impl == 7 || impl == 8 || impl == 9 || impl == 13) && (rep % nw_impl == 0 || nw_impl % rep == 0)) return impl;
+  return 1;
+}
+
+// the v2 launch of `impl` (7 / 8 / 9 / 13) on a bf16 cache, or (Q8) on the fp8 bytes kc / vc with the scales ksc / vsc
+template <bool Q8>
+static void launch_prefill_impl(int impl, const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const float* ksc,
+                                const float* vsc, const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask,
+                                int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int T, hipStream_t s) {
+  const int rep = H / Hkv;
+  if constexpr (Q8) {
+    // The fp8 staging needs ~6 registers beside the loop's, and only the 8-wave PIPE 2 loop has them (the 4-wave and
+    // the PIPE 1 instantiations spill: PIPE 1 issues the next tile's 16 scores MFMAs in one block). A wave computes the
+    // same bits in every pipelined form -- one q head x 32 queries over the same 64-key tiles, the same MFMA order,
+    // exp2(fma(s, scale, -m)) -- so impls 7 / 9 / 13 all run that one instantiation, impl 7 on its unpaired grid rule.
+    if (impl == 8)
+      launch_prefill_v2<4, 0, true>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep,
+                                    false, s);
     else
-      launch_prefill_v2<8, 2>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep, true, s);
+      launch_prefill_v2<8, 2, true>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep,
+                                    impl != 7, s);
+    return;
+  }
+  if (impl == 7)
+    launch_prefill_v2<4, 1, false>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep,
+                                   false, s);
+  else if (impl == 8)
+    launch_prefill_v2<4, 0, false>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep,
+                                   false, s);
+  else if (impl == 9)
+    launch_prefill_v2<8, 1, false>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep,
+                                   true, s);
+  else
+    launch_prefill_v2<8, 2, false>(q, kc, vc, ksc, vsc, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, rep,
+                                   true, s);
+}
+
+int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
+                 const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,
+                 hipStream_t s) {
+  if (B <= 0 || S <= 0) return 0;
+  if (Dh != AP_DH || H % Hkv) return -1;
+  const int impl = prefill_resolve_impl(B, S, H, Hkv);
+  if (impl != 1) {
+    launch_prefill_impl<false>(impl, q, kc, vc, nullptr, nullptr, slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv,
+                               T, s);
     JLA_CHECK_LAUNCH();
     return 0;
   }
   dim3 grid((S + AP_QB - 1) / AP_QB, H, B);
   attn_prefill_kernel<<<grid, 256, 0, s>>>(q, kc, vc, slot, kv_start, key_mask, mask_len, out, S, H, Hkv, T,
                                            1.f / sqrtf((float)Dh));
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+// The v2 launch straight on an FP8 KV cache: the impl attn_prefill would run at this shape, its Q8 instantiation.
+// Returns 1 where that is the v1 kernel (a GQA ratio v2 does not serve, impl 1 pinned): v1 has no fp8 staging, the
+// caller dequantises.
+int attn_prefill_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs,
+                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
+                    int B, int S, int H, int Hkv, int Dh, int T, hipStream_t s) {
+  if (Dh != AP_DH || Hkv < 1 || H % Hkv) return -1;
+  const int impl = prefill_resolve_impl(B, S, H, Hkv);
+  if (impl == 1) return 1;
+  // every pipelined impl runs the 8-wave instantiation here (launch_prefill_impl), so the GQA ratio has to fit 8 waves
+  // whatever the impl's own wave count is (a pinned impl 7 at rep 12 fits 4 waves only)
+  const int rep = H / Hkv;
+  if (impl != 8 && rep % 8 && 8 % rep) return 1;
+  if (B <= 0 || S <= 0) return 0;
+  launch_prefill_impl<true>(impl, q, reinterpret_cast<const bf16_t*>(kq), reinterpret_cast<const bf16_t*>(vq), ks, vs,
+                            slot, kv_start, key_mask, mask_len, out, B, S, H, Hkv, T, s);
   JLA_CHECK_LAUNCH();
   return 0;
 }

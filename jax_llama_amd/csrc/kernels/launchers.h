@@ -166,6 +166,7 @@ void attn_set_v6(int mode);
 void attn_set_v6_wpp(int wpp);
 void attn_set_q8_waves(int waves);  // the fp8 KV cache's kernel: 1 / 8 waves per pair pinned; 0: by shape
 void attn_set_q8_splits(int n);     // ... its key splits per pair: 0 by shape, 1 never, n > 1 pinned (the plan clamps it)
+void attn_set_q8_prefill(int mode);  // S > 1 on an fp8 cache: -1 by attn_prefill_q8_plan, 0 always dequantise, 1 always direct
 void attn_set_diag(int d);     // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)
 void attn_set_v6_diag(int d);  // tools only: v6 ablations (1 no compute, 2 no K loads, 4 no V DMAs; wrong results)
 // bounds-checked debug build: per-translation-unit error words (JLA_BOUNDS_* bits; 0 in release builds)
@@ -208,6 +209,12 @@ void attn_prefill_set_impl(int impl);  // 2 = GQA-shared MFMA 32x32 flash kernel
 int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                  const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,
                  hipStream_t s);
+// the same launch (the impl attn_prefill resolves at this shape) straight on an FP8 KV cache: the tiles are converted
+// while they are staged, bit-identical to attn_prefill on kv8_dequant's output. Returns 1 where the shape resolves to
+// the v1 kernel (impl 1 pinned, a GQA ratio v2 does not serve): the caller dequantises. Dh == 128.
+int attn_prefill_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs,
+                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
+                    int B, int S, int H, int Hkv, int Dh, int T, hipStream_t s);
 
 int argmax(const float* logits, int B, int V, int32_t* idx, float* val, hipStream_t s);
 // the (tgt, mx, se) triple of gemm_logprob from stored fp32 logits [B, V]

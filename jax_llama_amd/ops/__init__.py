@@ -804,10 +804,17 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
             e.attn_decode_q8(q, k_cache.q, k_cache.scale, v_cache.q, v_cache.scale, slot_t, kv_start, key_mask, out,
                              t_cap, ws, tickets)
         else:
-            # the rows the queries can see, dequantised (exact) into a scratch exactly that long: attn_prefill clamps
-            # the key rows it loads to its cache length, so it reads no scratch row that kv8_dequant did not write.
-            # A slot that lives on the device only (no host value without a sync): the whole cache.
+            # n: the rows a dequant pass would convert -- the rows the queries can see, or the whole cache for a slot
+            # that lives on the device only (no host value without a sync). The plan (csrc/kernels/attn_plan.h
+            # attn_prefill_q8_plan) says whether the flash kernel reads the fp8 bytes itself (one launch, no scratch;
+            # csrc/kernels/attn_prefill.hip, the same bits) ...
             n = k_cache.shape[2] if torch.is_tensor(slot0) else min(int(slot0) + s, k_cache.shape[2])
+            _rc, _why, direct = e.attn_prefill_q8_plan_check(bsz, h, k_cache.shape[1], s, n)
+            if direct and dh == 128 and e.attn_prefill_q8(q, k_cache.q, k_cache.scale, v_cache.q, v_cache.scale, slot_t,
+                                                          kv_start, key_mask, out):
+                return out
+            # ... or the rows are dequantised (exact) into a scratch exactly n long: attn_prefill clamps the key rows
+            # it loads to its cache length, so it reads no scratch row that kv8_dequant did not write
             kd, vd = kv8_dequant(k_cache, v_cache, n, scratch=True)
             e.attn_prefill(q, kd, vd, slot_t, kv_start, key_mask, out)
         return out
