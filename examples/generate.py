@@ -64,7 +64,7 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
 def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int = 256, temperature: float = 0.8,
          top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1,
          repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-         quantized_gemm: str = "dequant", top_k: int = 50):
+         quantized_gemm: str = "dequant", top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0):
     """Reference ``main`` (jax_example.py:33-40). ``num_beams > 1``: beam search (temperature is then taken as 0).
     Llama-3 (without beam search) stops on any of the tokenizer's ``stop_tokens`` (end of text, end of turn)."""
     generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache,
@@ -75,7 +75,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
     results = generator.generate_from_str(PROMPTS, max_gen_len=max_gen_len, temperature=temperature, top_p=top_p,
                                           num_beams=num_beams, repetition_penalty=repetition_penalty,
                                           no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens,
-                                          stop_token_ids=stops, top_k=top_k)
+                                          stop_token_ids=stops, top_k=top_k, min_p=min_p, typical_p=typical_p)
     if int(os.environ.get("RANK", "0")) == 0:
         for result in results:
             print(result)
@@ -86,7 +86,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
               weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1, repetition_penalty: float = 1.0,
               no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, quantized_gemm: str = "dequant",
-              top_k: int = 50):
+              top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -103,7 +103,7 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
                          dtype=torch.int32)
     gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0 and num_beams == 1,
                           temperature=temperature, top_p=top_p, top_k=top_k, pad_token_id=0, eos_token_id=-1,
-                          num_beams=num_beams,
+                          num_beams=num_beams, min_p=min_p, typical_p=typical_p,
                           repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
                           min_new_tokens=min_new_tokens)
     t0 = time.perf_counter()
@@ -126,6 +126,10 @@ if __name__ == "__main__":
     ap.add_argument("--top_p", type=float, default=0.95)
     ap.add_argument("--top_k", type=int, default=50,
                     help="0: no top-k cut (pure nucleus sampling with --top_p < 1, pure temperature sampling at 1)")
+    ap.add_argument("--min_p", type=float, default=0.0,
+                    help="keep the tokens with at least this fraction of the most likely token's probability (0: off)")
+    ap.add_argument("--typical_p", type=float, default=1.0,
+                    help="locally typical sampling: the tokens closest to the entropy, up to this mass (1: off)")
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--model", default="llama3-8b")
     ap.add_argument("--batch", type=int, default=2)
@@ -150,9 +154,11 @@ if __name__ == "__main__":
     a = ap.parse_args()
     if a.synthetic:
         synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
-                  a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k)
+                  a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k,
+                  a.min_p, a.typical_p)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
         main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
-             a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k)
+             a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k,
+             a.min_p, a.typical_p)

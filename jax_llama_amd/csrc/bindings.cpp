@@ -948,7 +948,7 @@ void topk_merge(Tensor cv, Tensor ci, int64_t k, int64_t mode, c10::optional<Ten
 
 // the full-vocabulary sampler: one token per row of fp32 logits [B, V] (top_k = 0: no top-k cut)
 void nucleus_sample(Tensor logits, int64_t top_k, double temperature, double top_p, int64_t seed, Tensor step,
-                    Tensor nxt, c10::optional<Tensor> kept) {
+                    Tensor nxt, c10::optional<Tensor> kept, double min_p, double typical_p) {
   for (auto* t : {&logits, &step, &nxt}) check_gpu(*t, "nucleus_sample arg");
   check(logits.scalar_type() == torch::kFloat32 && logits.dim() == 2 && logits.size(1) >= 1,
         "nucleus_sample: logits must be fp32 [B, V]");
@@ -956,6 +956,8 @@ void nucleus_sample(Tensor logits, int64_t top_k, double temperature, double top
   check(v <= jla::nucleus_sample_max_v(), "nucleus_sample: V above the kernel's limit");
   check(top_k >= 0 && top_k <= INT32_MAX, "nucleus_sample: top_k >= 0 (0 = the whole vocabulary)");
   check(temperature > 0 && top_p > 0, "nucleus_sample: temperature > 0 and top_p > 0");
+  check(min_p >= 0 && min_p <= 1 && typical_p > 0 && typical_p <= 1,
+        "nucleus_sample: min_p in [0, 1] and typical_p in (0, 1]");
   check(seed >= 0, "nucleus_sample: seed >= 0");
   check(step.scalar_type() == torch::kInt32 && step.numel() >= 1, "nucleus_sample: step int32 [1]");
   check(nxt.scalar_type() == torch::kInt32 && nxt.numel() == b, "nucleus_sample: nxt int32 [B]");
@@ -966,7 +968,7 @@ void nucleus_sample(Tensor logits, int64_t top_k, double temperature, double top
     kp = ptr<int32_t>(*kept);
   }
   rc(jla::nucleus_sample(ptr<float>(logits), b, v, (int)top_k, temperature, top_p, (uint64_t)seed,
-                         ptr<int32_t>(step), ptr<int32_t>(nxt), kp, stream()),
+                         ptr<int32_t>(step), ptr<int32_t>(nxt), kp, min_p, typical_p, stream()),
      "nucleus_sample");
 }
 
@@ -1547,7 +1549,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
         py::arg("out_v") = py::none(), py::arg("out_i") = py::none(), py::arg("nxt") = py::none(),
         py::arg("temperature") = 1.0, py::arg("top_p") = 1.0, py::arg("seed") = 0, py::arg("step") = py::none());
   m.def("nucleus_sample", &nucleus_sample, py::arg("logits"), py::arg("top_k"), py::arg("temperature"),
-        py::arg("top_p"), py::arg("seed"), py::arg("step"), py::arg("nxt"), py::arg("kept") = py::none());
+        py::arg("top_p"), py::arg("seed"), py::arg("step"), py::arg("nxt"), py::arg("kept") = py::none(),
+        py::arg("min_p") = 0.0, py::arg("typical_p") = 1.0);
   m.def("nucleus_sample_max_v", []() { return (int64_t)jla::nucleus_sample_max_v(); });
   m.def("decode_update", &decode_update);
   m.def("process_logits", &process_logits);

@@ -226,10 +226,11 @@ int topk_chunk(const float* logits, int B, int V, int K, int idx_offset, float* 
 int topk_merge(const float* cv, const int32_t* ci, int B, int C, int K, int mode, float* out_v, int32_t* out_i,
                int32_t* nxt, float temperature, float top_p, uint64_t seed, const int32_t* step, hipStream_t s);
 // full-vocabulary sampler (nucleus_sample.hip): top_k = 0 (all) or any k, top_p, one token per row into nxt[B];
-// kept (optional) [B] = the number of survivors. V <= nucleus_sample_max_v().
+// kept (optional) [B] = the number of survivors. V <= nucleus_sample_max_v(). min_p in [0, 1] (0: off) and typical_p
+// in (0, 1] (1: off) are the two further truncation rules, applied after top-k and top-p.
 int nucleus_sample_max_v();
 int nucleus_sample(const float* logits, int B, int V, int top_k, double temperature, double top_p, uint64_t seed,
-                   const int32_t* step, int32_t* nxt, int32_t* kept, hipStream_t s);
+                   const int32_t* step, int32_t* nxt, int32_t* kept, double min_p, double typical_p, hipStream_t s);
 // custom xGMI collectives over IPC-mapped uncached buffers (allreduce.hip)
 size_t car_buffer_bytes(long long max_bytes, int world);
 int car_alloc(long long max_bytes, int world, void** buf, void** sig, hipIpcMemHandle_t* hbuf, hipIpcMemHandle_t* hsig);

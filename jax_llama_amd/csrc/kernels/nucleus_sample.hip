@@ -28,6 +28,23 @@
 //                a group (counter = (i >> 2, row, step, 1): word 3 = 1 keeps the stream apart from topk_sample's).
 //                score = l + gumbel; thread best -> wave reduce -> LDS reduce, ties to the lower index.
 //
+// min_p and typical_p (template parameters MINP / TYP; with both off the kernel is the one above):
+//   min_p        token i passes iff mass_i >= min_mass = ceil(min_p * 2^40) (the product in fp64, on the host). The
+//                mass is monotone in the key, so the cut is a second lower bound on the key: kmin = the smallest key
+//                whose mass reaches min_mass, found once per row by bisection over the key bits (<= 32 evaluations).
+//                Alone it needs no descent: max sweep, then the draw. Call the survivors so far S2.
+//   typical      one sweep over S2 adds Z2 = sum mass_i and W = sum uint64(fp64(mass_i) * fp64(t_i)), t_i = m - l_i in
+//                fp32 (thread sums -> wave reduce -> LDS integer atomics: the same bits every call). With p_i =
+//                mass_i / Z2, -log p_i - H = t_i - h where h = W / Z2 (the log Z2 terms cancel), so the distance is
+//                d_i = |t_i - h| with h = fp32(fp64(W) / fp64(Z2)). d_i >= 0, so its bits are monotone, and ~bits(d_i)
+//                is a key whose descending order is d ascending: the same mass descent as top-p runs on that key over
+//                S2 only, with target ceil(typical_p * Z2), and the bins scanned "from the top" are the smallest
+//                distances. Its compaction reuses the LDS list (which then keeps the logit, from which key and mass
+//                follow); the first descent's tie index is settled before. Keys that tie in d need not have equal
+//                masses (one token above h and one below it), so the cut inside the tie group is an ordered mass scan:
+//                the index at which the group's cumulative mass, in index order, reaches the remaining target.
+//   kept         with either option the draw sweep counts the survivors it scores.
+//
 // LDS: 512 threads so that two workgroups share a CU; 2048 x (8 + 4) B of histograms + NS_CAP = 4096 x 8 B of list =
 // 56 KB, under the 64 KB a workgroup may declare statically and two of them under the CU's 160 KB.
 //
@@ -51,11 +68,13 @@ struct NsShared {
   uint32_t lkey[NS_CAP];  // compacted boundary bin: keys and vocabulary indices, in index order
   int32_t lidx[NS_CAP];
   uint32_t wsum[NS_WAVES];
+  u64_t wsum64[NS_WAVES];
+  u64_t z2, w;                           // typical: the mass of S2 and its mass-weighted sum of m - l
   u64_t sel_above_m, sel_bin_m, sel_tr;  // written by the scanning wave
   uint32_t sel_bin, sel_above_c, sel_bin_c;
   float red_s[NS_WAVES];
   int32_t red_i[NS_WAVES];
-  uint32_t red_k[NS_WAVES];
+  uint32_t red_k[NS_WAVES], red_c[NS_WAVES];
   int32_t tie_idx;
 };
 
@@ -87,27 +106,63 @@ JLA_DEV u64_t ns_mass(const NsRow& r, float x) {
   return (u64_t)(exp2f(__fsub_rn(ns_l(r, x), r.m) * 1.4426950408889634f) * 1099511627776.0f);
 }
 
-// exclusive block scan of one uint32 per thread; total = the block's sum
-JLA_DEV uint32_t ns_block_scan(uint32_t v, NsShared& sh, uint32_t& total) {
+// exclusive block scan of one value per thread (uint32 counts; uint64 masses); total = the block's sum
+template <typename T>
+JLA_DEV T ns_block_scan_in(T v, T* wsum, T& total) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  uint32_t incl = v;
+  T incl = v;
 #pragma unroll
   for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(incl, o, 64);
+    const T t = __shfl_up(incl, o, 64);
     if (lane >= o) incl += t;
   }
-  if (lane == 63) sh.wsum[w] = incl;
+  if (lane == 63) wsum[w] = incl;
   __syncthreads();
-  uint32_t base = 0, tot = 0;
+  T base = 0, tot = 0;
 #pragma unroll
   for (int i = 0; i < NS_WAVES; ++i) {
-    if (i < w) base += sh.wsum[i];
-    tot += sh.wsum[i];
+    if (i < w) base += wsum[i];
+    tot += wsum[i];
   }
   __syncthreads();
   total = tot;
   return base + incl - v;
 }
+JLA_DEV uint32_t ns_block_scan(uint32_t v, NsShared& sh, uint32_t& total) {
+  return ns_block_scan_in(v, sh.wsum, total);
+}
+JLA_DEV u64_t ns_block_scan(u64_t v, NsShared& sh, u64_t& total) { return ns_block_scan_in(v, sh.wsum64, total); }
+
+// The survivors of top-k / top-p (S1: key > T, and key == T up to index tie_idx) and of min_p (key >= kmin).
+struct NsKeep {
+  bool all;  // no top-k and no top-p cut
+  uint32_t T, kmin;
+  int32_t tie_idx;
+  JLA_DEV bool operator()(uint32_t key, int i) const {
+    return (all || key > T || (key == T && i <= tie_idx)) && key >= kmin;
+  }
+};
+
+// What a descent orders by. in(): whether token i takes part; key(): a larger key comes earlier; pack() / unpack():
+// the word the compacted list keeps of a token, and the key and logit it gives back.
+struct NsLogitKey {
+  JLA_DEV bool in(int, float) const { return true; }
+  JLA_DEV uint32_t key(float x) const { return fkey(x); }
+  JLA_DEV uint32_t pack(float, uint32_t key) const { return key; }
+  JLA_DEV void unpack(uint32_t u, uint32_t& key, float& x) const { key = u, x = kfloat(u); }
+};
+// typical: over S2, by the distance d = |(m - l) - h| ascending
+struct NsTypicalKey {
+  NsRow r;
+  NsKeep keep;
+  float h;
+  JLA_DEV bool in(int i, float x) const { return keep(fkey(x), i); }
+  JLA_DEV uint32_t key(float x) const {
+    return ~__float_as_uint(fabsf(__fadd_rn(__fsub_rn(ns_l(r, x), r.m), h)));
+  }
+  JLA_DEV uint32_t pack(float x, uint32_t) const { return __float_as_uint(x); }
+  JLA_DEV void unpack(uint32_t u, uint32_t& key, float& x) const { x = __uint_as_float(u), key = this->key(x); }
+};
 
 // Wave 0 scans bins nb-1 .. 0: the boundary bin of the count target kr (first bin at which the cumulative count
 // reaches kr) or of the mass target tr (first at which the cumulative mass reaches tr). frac > 0: tr is not known yet
@@ -168,13 +223,15 @@ JLA_DEV void ns_flush(NsShared& sh, NsAcc& a, bool with_mass) {
 struct NsCut {
   uint32_t T, n_eq, c_eq, kept;  // survivors: key > T and the first n_eq of the c_eq keys == T; kept of them in all
   u64_t z;                       // count descent: the survivors' mass
+  u64_t tr;                      // mass descent: what of the target is left for the keys == T
   uint32_t n_list;               // > 0: the LDS list holds the first pass's boundary bin
 };
 
 // BY_MASS false: the k largest keys (with_mass: also their mass, in z). BY_MASS true: the ranks with less than
-// ceil(top_p * Z) of mass before them, Z = z_known or (0) the row's total.
-template <bool BY_MASS>
-JLA_DEV NsCut ns_descend(const NsRow& r, NsShared& sh, bool with_mass, uint32_t k, double top_p, u64_t z_known) {
+// ceil(top_p * Z) of mass before them, Z = z_known or (0) the row's total. kf: the order and the tokens it ranges over.
+template <bool BY_MASS, typename K>
+JLA_DEV NsCut ns_descend(const K& kf, const NsRow& r, NsShared& sh, bool with_mass, uint32_t k, double top_p,
+                         u64_t z_known) {
   uint32_t prefix = 0, mask = 0, kr = k, acc_c = 0, bin_c = 0, n_list = 0;
   u64_t tr = BY_MASS && z_known ? (u64_t)ceil((double)z_known * top_p) : 0, acc_m = 0, bin_m = 0;
   for (int pass = 0; pass < 3; ++pass) {
@@ -193,14 +250,19 @@ JLA_DEV NsCut ns_descend(const NsRow& r, NsShared& sh, bool with_mass, uint32_t 
       if (with_mass) acc.m += ns_mass(r, x);
     };
     if (n_list) {
-      for (int j = threadIdx.x; j < (int)n_list; j += NS_THREADS) add(sh.lkey[j], kfloat(sh.lkey[j]));
+      for (int j = threadIdx.x; j < (int)n_list; j += NS_THREADS) {
+        uint32_t key;
+        float x;
+        kf.unpack(sh.lkey[j], key, x);
+        add(key, x);
+      }
     } else {
       for (int i4 = threadIdx.x; i4 < r.n4; i4 += NS_THREADS) {
         float v[4];
         const int n = ns_load4(r, i4, v);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          if (q < n) add(fkey(v[q]), v[q]);
+          if (q < n && kf.in(4 * i4 + q, v[q])) add(kf.key(v[q]), v[q]);
       }
     }
     ns_flush(sh, acc, with_mass);
@@ -223,15 +285,15 @@ JLA_DEV NsCut ns_descend(const NsRow& r, NsShared& sh, bool with_mass, uint32_t 
         uint32_t key[4], c = 0;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          key[q] = q < n ? fkey(v[q]) : 0u;
-          c += q < n && (key[q] & mask) == prefix;
+          key[q] = q < n && kf.in(4 * i4 + q, v[q]) ? kf.key(v[q]) : ~prefix;  // (~prefix never matches)
+          c += (key[q] & mask) == prefix;
         }
         uint32_t tot;
         uint32_t pos = base + ns_block_scan(c, sh, tot);
 #pragma unroll
         for (int q = 0; q < 4; ++q)
-          if (q < n && (key[q] & mask) == prefix && pos < (uint32_t)NS_CAP) {
-            sh.lkey[pos] = key[q];
+          if ((key[q] & mask) == prefix && pos < (uint32_t)NS_CAP) {
+            sh.lkey[pos] = kf.pack(v[q], key[q]);
             sh.lidx[pos] = 4 * i4 + q;
             ++pos;
           }
@@ -242,7 +304,7 @@ JLA_DEV NsCut ns_descend(const NsRow& r, NsShared& sh, bool with_mass, uint32_t 
     }
   }
   NsCut cut;
-  cut.T = prefix, cut.c_eq = bin_c, cut.n_list = n_list;
+  cut.T = prefix, cut.c_eq = bin_c, cut.n_list = n_list, cut.tr = tr;
   const u64_t mu = bin_m / max(bin_c, 1u);  // the keys of the last bin are equal, and so are their masses
   if (BY_MASS) {
     cut.n_eq = mu ? (uint32_t)min((u64_t)bin_c, (tr + mu - 1) / mu) : bin_c;
@@ -282,6 +344,51 @@ JLA_DEV int32_t ns_nth_tie(NsShared& sh, int ngroups, uint32_t T, uint32_t n_eq,
   return sh.tie_idx;
 }
 
+// typical's tie group, whose masses may differ: the vocabulary index of the first key == T, in index order, at which
+// the group's cumulative mass reaches tr (1 <= tr <= the group's mass). get(g, hit, idx, ms) yields group g's entries,
+// hit = "takes part and key == T", and returns how many. (Unequal masses inside a tie group come only from two fp32
+// distances that round to the same bits on either side of h: no exact-grid row has them, and no test does.)
+template <typename G>
+JLA_DEV int32_t ns_mass_tie(NsShared& sh, int ngroups, u64_t tr, G&& get) {
+  u64_t seen = 0;
+  if (threadIdx.x == 0) sh.tie_idx = 0x7fffffff;
+  for (int t0 = 0; t0 < ngroups && seen < tr; t0 += NS_THREADS) {  // seen is uniform: so is the trip count
+    bool hit[4] = {};
+    int32_t idx[4] = {};
+    u64_t ms[4] = {}, c = 0;
+    const int n = t0 + (int)threadIdx.x < ngroups ? get(t0 + (int)threadIdx.x, hit, idx, ms) : 0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      hit[q] = q < n && hit[q];
+      c += hit[q] ? ms[q] : 0;
+    }
+    u64_t tot;
+    u64_t ex = seen + ns_block_scan(c, sh, tot);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (hit[q]) {
+        if (ex < tr && tr <= ex + ms[q]) sh.tie_idx = idx[q];  // exactly one entry of the group
+        ex += ms[q];
+      }
+    seen += tot;
+  }
+  __syncthreads();
+  return sh.tie_idx;
+}
+
+// min_p as a bound on the key: the smallest key whose mass reaches min_mass (the row maximum's, 2^40, always does).
+// The bisection takes ns_mass to be monotone in the key; the device's exp2f is not formally so, and a local inversion
+// would put kmin a key ulp or two beside the per-token test mass >= min_mass (far inside the definition's rounding).
+JLA_DEV uint32_t ns_min_key(const NsRow& r, uint32_t kmax, u64_t min_mass) {
+  uint32_t lo = fkey(-INFINITY), hi = kmax;
+  while (lo < hi) {
+    const uint32_t mid = lo + ((hi - lo) >> 1);
+    if (ns_mass(r, kfloat(mid)) >= min_mass) hi = mid;
+    else lo = mid + 1;
+  }
+  return lo;
+}
+
 // -log(-log(u)), u = (n + 0.5) / 2^24 with n = the word's top 24 bits. Both branches feed exact fp32 arguments: the
 // upper half of the range goes through log1p(-(1 - u)), where the winners of a long row live (u within 1e-5 of 1).
 JLA_DEV float ns_gumbel(uint32_t w) {
@@ -291,10 +398,12 @@ JLA_DEV float ns_gumbel(uint32_t w) {
   return -logf(a);
 }
 
+// MINP: min_mass > 0 is the min_p cut. TYP: typical_p < 1 is the typical cut.
+template <bool MINP, bool TYP>
 __global__ void __launch_bounds__(NS_THREADS)
     nucleus_sample_kernel(const float* __restrict__ logits, int V, int k, float inv_t, double top_p, int vec,
                           uint32_t seed_lo, uint32_t seed_hi, const int32_t* __restrict__ step,
-                          int32_t* __restrict__ nxt, int32_t* __restrict__ kept) {
+                          int32_t* __restrict__ nxt, int32_t* __restrict__ kept, u64_t min_mass, double typical_p) {
   __shared__ NsShared sh;
   const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   NsRow r;
@@ -325,8 +434,8 @@ __global__ void __launch_bounds__(NS_THREADS)
   int32_t tie_idx = 0x7fffffff;
   if (!all) {
     NsCut cut;
-    if (use_k) cut = ns_descend<false>(r, sh, use_p, (uint32_t)k, 0.0, 0);
-    if (use_p) cut = ns_descend<true>(r, sh, true, 0, top_p, use_k ? cut.z : 0);
+    if (use_k) cut = ns_descend<false>(NsLogitKey{}, r, sh, use_p, (uint32_t)k, 0.0, 0);
+    if (use_p) cut = ns_descend<true>(NsLogitKey{}, r, sh, true, 0, top_p, use_k ? cut.z : 0);
     T = cut.T, n_kept = cut.kept;
     if (cut.n_eq < cut.c_eq) {
       if (cut.n_list)
@@ -348,11 +457,63 @@ __global__ void __launch_bounds__(NS_THREADS)
         });
     }
   }
+  const NsKeep keep{all, T, MINP ? ns_min_key(r, kmax, min_mass) : 0u, tie_idx};
+
+  // typical: Z2 and W over S2 give h; then the mass descent on the distance key, and the cut inside its tie group
+  NsTypicalKey tk{r, keep, 0.f};
+  uint32_t Td = 0;
+  int32_t tie_d = 0x7fffffff;
+  if (TYP) {
+    if (threadIdx.x == 0) sh.z2 = 0, sh.w = 0;
+    __syncthreads();
+    u64_t z = 0, w = 0;
+    for (int i4 = threadIdx.x; i4 < r.n4; i4 += NS_THREADS) {
+      float v[4];
+      const int n = ns_load4(r, i4, v);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (!(q < n && keep(fkey(v[q]), 4 * i4 + q))) continue;
+        const u64_t mass = ns_mass(r, v[q]);
+        if (mass) z += mass, w += (u64_t)((double)mass * (double)__fsub_rn(r.m, ns_l(r, v[q])));  // (mass 0: l = -inf)
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) z += __shfl_xor(z, o, 64), w += __shfl_xor(w, o, 64);
+    if (lane == 0) atomicAdd(&sh.z2, z), atomicAdd(&sh.w, w);
+    __syncthreads();
+    tk.h = (float)((double)sh.w / (double)sh.z2);
+    const NsCut cut = ns_descend<true>(tk, r, sh, true, 0, typical_p, sh.z2);
+    Td = cut.T;
+    if (cut.c_eq > 1) {
+      if (cut.n_list)
+        tie_d = ns_mass_tie(sh, ((int)cut.n_list + 3) >> 2, cut.tr,
+                            [&](int g, bool(&hit)[4], int32_t(&idx)[4], u64_t(&ms)[4]) {
+          const int n = min(4, (int)cut.n_list - 4 * g);
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            if (q < n) {
+              const float x = __uint_as_float(sh.lkey[4 * g + q]);
+              hit[q] = tk.key(x) == Td, idx[q] = sh.lidx[4 * g + q], ms[q] = ns_mass(r, x);
+            }
+          return n;
+        });
+      else
+        tie_d = ns_mass_tie(sh, r.n4, cut.tr, [&](int g, bool(&hit)[4], int32_t(&idx)[4], u64_t(&ms)[4]) {
+          float v[4];
+          const int n = ns_load4(r, g, v);
+#pragma unroll
+          for (int q = 0; q < 4; ++q)
+            hit[q] = tk.in(4 * g + q, v[q]) && tk.key(v[q]) == Td, idx[q] = 4 * g + q, ms[q] = ns_mass(r, v[q]);
+          return n;
+        });
+    }
+  }
 
   // draw: Gumbel-max over the survivors, noise keyed by the vocabulary index
   const uint32_t st = (uint32_t)step[0];
   float best = -INFINITY;
   int32_t bi = 0x7fffffff;
+  uint32_t drawn = 0;  // (MINP or TYP) the survivors, counted where they are scored
   for (int i4 = threadIdx.x; i4 < r.n4; i4 += NS_THREADS) {
     float v[4];
     const int n = ns_load4(r, i4, v);
@@ -360,7 +521,13 @@ __global__ void __launch_bounds__(NS_THREADS)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const uint32_t key = fkey(v[q]);
-      s[q] = q < n && (all || key > T || (key == T && 4 * i4 + q <= tie_idx));
+      s[q] = q < n && (all || key > T || (key == T && 4 * i4 + q <= tie_idx));  // (keep, written out)
+      if (MINP) s[q] = s[q] && key >= keep.kmin;
+      if (TYP) {
+        const uint32_t dk = tk.key(v[q]);
+        s[q] = s[q] && (dk > Td || (dk == Td && 4 * i4 + q <= tie_d));
+      }
+      if (MINP || TYP) drawn += s[q];
       any |= s[q];
     }
     if (!any) continue;
@@ -379,12 +546,21 @@ __global__ void __launch_bounds__(NS_THREADS)
     const int32_t oi = __shfl_xor(bi, o, 64);
     if (os > best || (os == best && oi < bi)) best = os, bi = oi;
   }
+  if (MINP || TYP) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) drawn += __shfl_xor(drawn, o, 64);
+    if (lane == 0) sh.red_c[wave] = drawn;
+  }
   if (lane == 0) sh.red_s[wave] = best, sh.red_i[wave] = bi;
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int i = 1; i < NS_WAVES; ++i)
       if (sh.red_s[i] > best || (sh.red_s[i] == best && sh.red_i[i] < bi)) best = sh.red_s[i], bi = sh.red_i[i];
     nxt[b] = min(bi, V - 1);  // (a row outside the contract, NaN throughout, still yields a token of the vocabulary)
+    if (MINP || TYP) {
+      n_kept = 0;
+      for (int i = 0; i < NS_WAVES; ++i) n_kept += sh.red_c[i];
+    }
     if (kept) kept[b] = (int32_t)n_kept;
   }
 }
@@ -394,15 +570,20 @@ __global__ void __launch_bounds__(NS_THREADS)
 int nucleus_sample_max_v() { return NS_MAX_V; }
 
 int nucleus_sample(const float* logits, int B, int V, int top_k, double temperature, double top_p, uint64_t seed,
-                   const int32_t* step, int32_t* nxt, int32_t* kept, hipStream_t s) {
+                   const int32_t* step, int32_t* nxt, int32_t* kept, double min_p, double typical_p, hipStream_t s) {
   if (B <= 0) return 0;
   if (V < 1 || V > NS_MAX_V || top_k < 0) return -1;
   if (!logits || !step || !nxt || !(temperature > 0.0) || !(top_p > 0.0)) return -2;
+  if (!(min_p >= 0.0 && min_p <= 1.0) || !(typical_p > 0.0 && typical_p <= 1.0)) return -2;
   const int k = top_k == 0 ? V : min(top_k, V);
   const int vec = (V & 3) == 0 && V >= 1024 && (reinterpret_cast<uintptr_t>(logits) & 15) == 0;
   const float inv_t = (float)(1.0 / temperature);  // fp64, rounded once (process_logits' convention)
-  nucleus_sample_kernel<<<B, NS_THREADS, 0, s>>>(logits, V, k, inv_t, top_p, vec, (uint32_t)seed,
-                                                 (uint32_t)(seed >> 32), step, nxt, kept);
+  const u64_t min_mass = (u64_t)ceil(min_p * 1099511627776.0);  // 0: no min_p cut
+  const bool typ = typical_p < 1.0;
+  auto* kern = min_mass ? (typ ? nucleus_sample_kernel<true, true> : nucleus_sample_kernel<true, false>)
+                        : (typ ? nucleus_sample_kernel<false, true> : nucleus_sample_kernel<false, false>);
+  kern<<<B, NS_THREADS, 0, s>>>(logits, V, k, inv_t, top_p, vec, (uint32_t)seed, (uint32_t)(seed >> 32), step, nxt,
+                                kept, min_mass, typical_p);
   JLA_CHECK_LAUNCH();
   return 0;
 }

@@ -1058,8 +1058,9 @@ NUCLEUS_MAX_V = 1 << 22  # nucleus_sample.hip: the row's integer masses (2^40 ea
 
 
 def nucleus_sample(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: torch.Tensor,
-                   comm=None, return_kept: bool = False):
-    """temperature -> top-k (``top_k`` 0 or None: none) -> top-p -> categorical over the whole vocabulary, one launch
+                   comm=None, return_kept: bool = False, min_p: float = 0.0, typical_p: float = 1.0):
+    """temperature -> top-k (``top_k`` 0 or None: none) -> top-p -> min-p (``min_p`` 0: none) -> typical
+    (``typical_p`` 1: none) -> categorical over the whole vocabulary, one launch
     per call (csrc/kernels/nucleus_sample.hip; ``ref.nucleus_sample`` is the definition): threshold select by radix
     descent, then Gumbel-max with noise keyed by the vocabulary index. Under TP the logits are all-gathered and every
     rank runs the whole row: index-keyed noise makes the ranks agree without a second exchange. ``step`` is a device
@@ -1075,11 +1076,18 @@ def nucleus_sample(logits: torch.Tensor, top_k, temperature: float, top_p: float
     top_p = 1.0 if top_p is None else float(top_p)
     if not top_p > 0:
         raise ValueError("nucleus_sample: top_p > 0")
+    min_p, typical_p = float(min_p), float(typical_p)
+    if not 0.0 <= min_p <= 1.0:
+        raise ValueError("nucleus_sample: min_p in [0, 1] (0: no min-p cut)")
+    if not 0.0 < typical_p <= 1.0:
+        raise ValueError("nucleus_sample: typical_p in (0, 1] (1: no typical cut)")
     if not _is_gpu(x):
-        return ref.nucleus_sample(x, top_k, temperature, top_p, seed, int(step.reshape(-1)[0]), return_kept)
+        return ref.nucleus_sample(x, top_k, temperature, top_p, seed, int(step.reshape(-1)[0]), return_kept,
+                                  min_p, typical_p)
     nxt = torch.empty(b, dtype=torch.int32, device=x.device)
     kept = torch.empty(b, dtype=torch.int32, device=x.device) if return_kept else None
-    ext().nucleus_sample(x, int(top_k or 0), float(temperature), top_p, int(seed) & ((1 << 63) - 1), step, nxt, kept)
+    ext().nucleus_sample(x, int(top_k or 0), float(temperature), top_p, int(seed) & ((1 << 63) - 1), step, nxt, kept,
+                         min_p=min_p, typical_p=typical_p)
     return (nxt, kept) if return_kept else nxt
 
 

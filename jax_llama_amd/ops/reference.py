@@ -580,23 +580,39 @@ def topk_sample(logits: torch.Tensor, k: int, temperature: float, top_p: float, 
     return idx[torch.arange(b), torch.from_numpy(choice)].to(torch.int32)
 
 
-def nucleus_scores(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: int):
+def nucleus_scores(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: int,
+                   min_p: float = 0.0, typical_p: float = 1.0, cuts: list = None):
     """The full-vocabulary sampler's definition in float64 (README "Full-vocabulary sampling"), row by row: a list of
     ``(idx, score)``, the survivors' vocabulary indices (ascending) and their Gumbel scores ``l + g``.
 
     Rank = position by raw logit descending, ties to the lower index. top-k keeps the first ``k`` ranks (``top_k`` 0 or
     None: all). top-p (only when ``top_p < 1``): with ``l = x * fp32(1 / temperature)`` and ``e = exp(l - max l)``,
     rank r survives iff the sum of ``e`` over the ranks before it is ``< top_p * Z``, ``Z`` = the sum over the top-k
-    survivors; rank 0 always survives. Noise: ``g_i = -log(-log(u_i))``, ``u_i = ((w >> 8) + 0.5) / 2^24``, ``w`` =
+    survivors; rank 0 always survives. min_p (only when ``0 < min_p <= 1``, HF's order: after top-p): a survivor stays
+    iff ``e_i >= min_p`` (HF's ``p_i >= min_p * p_max``; the row maximum always stays). typical_p (only when
+    ``0 < typical_p < 1``), over the survivors so far: ``Z2 = sum e``, ``p = e / Z2``, ``H = -sum p log p``,
+    ``d = |-log p - H|``; ordered by ``d`` ascending, ties to the lower index, position r survives iff the ``e`` of the
+    positions before it sum to ``< typical_p * Z2``; position 0 always survives. ``-inf`` logits have ``e = 0``, add 0
+    to ``H`` and have ``d = inf``. Noise: ``g_i = -log(-log(u_i))``, ``u_i = ((w >> 8) + 0.5) / 2^24``, ``w`` =
     word ``i & 3`` of ``philox4x32_10((i >> 2, row, step, 1), seed)`` with ``i`` the vocabulary index. A row that is
-    all ``-inf`` counts as a row of equal logits."""
+    all ``-inf`` counts as a row of equal logits. ``cuts`` (a list) receives every comparison made, as ``(values,
+    threshold)``: the masses before the ranks against ``top_p * Z``, ``e`` against ``min_p``, the masses before the typical
+    positions against ``typical_p * Z2`` and the distances that differ from the last survivor's against that distance:
+    how far a row's decisions are from their thresholds (the tests' margin condition).
+
+    The kernel's arithmetic (csrc/kernels/nucleus_sample.hip), where it rounds differently: ``l`` and ``l - max l`` in
+    fp32; masses are the integers ``uint64(exp2((l - m) * log2e) * 2^40)``; the top-p and typical targets are
+    ``ceil(p * Z)`` on the integer sums with the product in fp64; min_p keeps ``mass_i >= ceil(min_p * 2^40)`` (product
+    in fp64), applied as a bound on the logit's key found by bisection; ``d_i = |fp32(m - l_i) - h|`` in fp32 with
+    ``h = fp32(W / Z2)``, ``W = sum uint64(fp64(mass_i) * fp64(m - l_i))`` and ``Z2 = sum mass_i`` exact integer sums
+    (``-log p_i - H = (m - l_i) - W / Z2``: the ``log Z2`` terms cancel, so ``H`` itself is never formed)."""
     import numpy as np
     x32 = logits.detach().float().cpu().numpy()
     b, v = x32.shape
     k = v if not top_k else min(int(top_k), v)
     inv_t = float(np.float32(1.0 / float(temperature)))
     key = (seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
-    out = []
+    out, cuts = [], [] if cuts is None else cuts
     for r in range(b):
         x = x32[r].astype(np.float64)
         if np.all(np.isneginf(x)):
@@ -609,6 +625,22 @@ def nucleus_scores(logits: torch.Tensor, top_k, temperature: float, top_p: float
             keep = before < float(top_p) * e.sum()
             keep[0] = True
             order = order[keep]
+            cuts.append((before[1:], float(top_p) * e.sum()))
+        if min_p:
+            cuts.append((np.exp(l[order] - l[order[0]]), float(min_p)))
+            order = order[cuts[-1][0] >= float(min_p)]
+        if typical_p is not None and typical_p < 1.0:
+            e = np.exp(l[order] - l[order[0]])
+            p = e / e.sum()
+            with np.errstate(divide="ignore", invalid="ignore"):
+                nlp = -np.log(p)
+                d = np.abs(nlp - np.where(p > 0, p * nlp, 0.0).sum())
+            by_d = np.lexsort((order, d))
+            keep = np.cumsum(e[by_d]) - e[by_d] < float(typical_p) * e.sum()
+            keep[0] = True
+            cuts.append(((np.cumsum(e[by_d]) - e[by_d])[1:], float(typical_p) * e.sum()))
+            cuts.append((d[d != d[by_d[keep]][-1]], d[by_d[keep]][-1]))
+            order = order[by_d[keep]]
         idx = np.sort(order)
         grp, inv = np.unique(idx >> 2, return_inverse=True)
         ctr = np.zeros((grp.size, 4), dtype=np.uint32)
@@ -620,12 +652,12 @@ def nucleus_scores(logits: torch.Tensor, top_k, temperature: float, top_p: float
 
 
 def nucleus_sample(logits: torch.Tensor, top_k, temperature: float, top_p: float, seed: int, step: int,
-                   return_kept: bool = False):
+                   return_kept: bool = False, min_p: float = 0.0, typical_p: float = 1.0):
     """int32 ``[B]``: per row the argmax of ``nucleus_scores`` (ties to the lower index); with ``return_kept`` also
     the number of survivors, int32 ``[B]``. The noise is keyed by vocabulary index with Philox counter word 3 = 1
     (``topk_sample``: by rank, word 3 = 0), so one seed draws different tokens at ``top_k`` = 64 and 65."""
     import numpy as np
-    rows = nucleus_scores(logits, top_k, temperature, top_p, seed, step)
+    rows = nucleus_scores(logits, top_k, temperature, top_p, seed, step, min_p, typical_p)
     tok = torch.tensor([int(idx[np.argmax(s)]) for idx, s in rows], dtype=torch.int32)
     if return_kept:
         return tok, torch.tensor([idx.size for idx, _ in rows], dtype=torch.int32)

@@ -52,6 +52,8 @@ class GenerationConfig:
     temperature: float = 1.0
     top_k: int = 50  # HF default; the reference never overrides it
     top_p: float = 1.0
+    min_p: float = 0.0  # HF's min-p warper: keep p_i >= min_p * p_max (0: off)
+    typical_p: float = 1.0  # HF's typical warper (1: off); both in the README's "Full-vocabulary sampling"
     num_beams: int = 1
     pad_token_id: Optional[int] = None
     eos_token_id: object = None  # one id, or a list of 1 .. 8 ids (the stop set)
@@ -113,11 +115,26 @@ def processors_active(gc: GenerationConfig) -> bool:
             or ((gc.min_length > 0 or gc.min_new_tokens > 0) and bool(stop_ids(gc))))
 
 
+def truncation_active(gc: GenerationConfig) -> bool:
+    """Whether ``min_p`` or ``typical_p`` cuts anything: only the full-vocabulary sampler knows the two rules."""
+    return gc.min_p > 0.0 or gc.typical_p < 1.0
+
+
 def validate_processors(gc: GenerationConfig, vocab: int) -> None:
     """ValueError for settings outside the definition (``generate`` and ``DecodeEngine.run`` both call it)."""
     p = gc.repetition_penalty
     if isinstance(p, bool) or not isinstance(p, (int, float)) or not p > 0:
         raise ValueError(f"repetition_penalty must be a number > 0, got {p!r}")
+    for name in ("min_p", "typical_p"):
+        val = getattr(gc, name)
+        if isinstance(val, bool) or not isinstance(val, (int, float)):
+            raise ValueError(f"{name} must be a number (min_p 0 and typical_p 1 are \"off\"), got {val!r}")
+    if not 0.0 <= gc.min_p <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1] (0: off), got {gc.min_p!r}")
+    if not 0.0 < gc.typical_p <= 1.0:
+        raise ValueError(f"typical_p must be in (0, 1] (1: off), got {gc.typical_p!r}")
+    if gc.num_beams != 1 and truncation_active(gc):
+        raise ValueError("beam search does not sample: num_beams > 1 takes no min_p and no typical_p")
     for name in ("no_repeat_ngram_size", "min_length", "min_new_tokens"):
         val = getattr(gc, name)
         if isinstance(val, bool) or not isinstance(val, int) or val < 0:
@@ -160,9 +177,28 @@ def _sampler_route(gc: GenerationConfig, v_local: int, tp: int, on_cpu: bool, ha
     k = min(gc.top_k or 0, v)
     if not (has_step and gc.temperature and gc.temperature > 0):
         return "torch"
+    if truncation_active(gc):  # topk_sample does not know min_p / typical_p: every top_k goes to the full sampler
+        return "nucleus" if v <= ops.NUCLEUS_MAX_V else "torch"
     if 1 <= k <= ops.SAMPLER_MAX_K and (on_cpu or ops.ext().topk_chunks(v_local) * min(k, v_local) <= 4096):
         return "topk"
     return "nucleus" if v <= ops.NUCLEUS_MAX_V else "torch"
+
+
+def _min_p_typical(vals: torch.Tensor, gc: GenerationConfig) -> torch.Tensor:
+    """The torch path's min_p and typical_p: ``vals`` [B, k], sorted descending with the cut entries at -inf; returns
+    them with what the two rules cut at -inf as well (ties in the distance in sort order)."""
+    if gc.min_p > 0.0:  # vals[:, 0] is the row maximum: e_i >= min_p
+        vals = torch.where(torch.exp(vals - vals[:, :1]) >= gc.min_p, vals, torch.full_like(vals, _NEG_INF))
+    if gc.typical_p < 1.0:
+        logp = torch.log_softmax(vals, -1)
+        p = logp.exp()
+        ent = -torch.where(p > 0, p * logp, torch.zeros_like(p)).sum(-1, keepdim=True)
+        _, by_d = torch.sort((-logp - ent).abs(), dim=-1, stable=True)
+        ps = p.gather(1, by_d)
+        keep = (ps.cumsum(-1) - ps) < gc.typical_p
+        keep[:, 0] = True
+        vals = torch.where(torch.zeros_like(keep).scatter(1, by_d, keep), vals, torch.full_like(vals, _NEG_INF))
+    return vals
 
 
 def _sample(model, logits_local: torch.Tensor, gc: GenerationConfig, gen: Optional[torch.Generator],
@@ -174,8 +210,10 @@ def _sample(model, logits_local: torch.Tensor, gc: GenerationConfig, gen: Option
     top_k = 0 / None (pure nucleus or pure temperature sampling), top_k > 64, or more top-k candidates than the merge
     takes: the full-vocabulary sampler (ops.nucleus_sample: one launch per step, threshold select + Gumbel-max keyed by
     the vocabulary index; under TP on the gathered logits), graph-capturable and identical on CPU as well.
+    ``min_p`` > 0 or ``typical_p`` < 1 (HF's order: after top-p) send every ``top_k`` to the full-vocabulary sampler,
+    the only kernel that knows the two rules; at ``top_k`` <= 64 that changes the Philox stream.
     The torch sort path is left for what neither takes: no device ``step`` (a caller outside the decode loop), or a
-    vocabulary above ops.NUCLEUS_MAX_V."""
+    vocabulary above ops.NUCLEUS_MAX_V; it applies the same four rules."""
     comm = model.comm
     v_local = logits_local.shape[1]
     k = min(gc.top_k or 0, v_local * comm.size)
@@ -185,7 +223,7 @@ def _sample(model, logits_local: torch.Tensor, gc: GenerationConfig, gen: Option
                                gc.seed, step, comm if comm.size > 1 else None)
     if route == "nucleus":
         return ops.nucleus_sample(logits_local, gc.top_k or 0, gc.temperature, gc.top_p, gc.seed, step,
-                                  comm if comm.size > 1 else None)
+                                  comm if comm.size > 1 else None, min_p=gc.min_p, typical_p=gc.typical_p)
     x = logits_local.float()
     if gc.temperature is not None and gc.temperature != 1.0:
         x = x / gc.temperature
@@ -207,6 +245,7 @@ def _sample(model, logits_local: torch.Tensor, gc: GenerationConfig, gen: Option
         keep = torch.roll(cum < gc.top_p, 1, dims=-1)
         keep[:, 0] = True
         vals = torch.where(keep, vals, torch.full_like(vals, _NEG_INF))
+    vals = _min_p_typical(vals, gc)
     u = torch.rand(vals.shape, device=vals.device, generator=gen, dtype=torch.float32)
     gumbel = -torch.log(-torch.log(u.clamp_min(1e-20)).clamp_min(1e-20))
     choice = (vals + gumbel).argmax(-1)
@@ -393,7 +432,8 @@ class DecodeEngine:
         # With processors or a stop list the key grows by their by-value arguments: the penalty (and with it 1 / p)
         # and the n-gram size. The ids, the minimum length and the history starts are read from this engine's buffers.
         gc = self.gc
-        sampler = (gc.top_k, gc.temperature, gc.top_p, int(gc.seed)) if gc.do_sample else None
+        sampler = ((gc.top_k, gc.temperature, gc.top_p, int(gc.seed), float(gc.min_p), float(gc.typical_p))
+                   if gc.do_sample else None)
         key = (gc.do_sample, self.key_mask is not None, ops.workspace.generation, _fused_greedy(),
                ops.ARGMAX_FUSED_MIN_M, ops.SKINNY_ARGMAX, ops.QKV_ATTN, self.model.comm.reduce_dtype,
                int(gc.pad_token_id), None if self._stop_set else int(gc.eos_token_id), sampler)

@@ -43,6 +43,8 @@ def main():
     ap.add_argument("--min-new-tokens", type=int, default=0,
                     help="with any of these three logits-processor settings every point is measured with the "
                     "processors off and on, alternately (record field `processors`)")
+    ap.add_argument("--min-p", type=float, default=0.0, help="with --sample: every point with min_p off and on, "
+                    "alternately (record field `min_p`; on, every top_k runs the full-vocabulary sampler)")
     ap.add_argument("--tune-report", action="store_true", help="print the decode-kernel choices and the graph-timed "
                     "microseconds of every candidate measured (ops/autotune.py)")
     args = ap.parse_args()
@@ -66,18 +68,21 @@ def main():
                                  min_new_tokens=args.min_new_tokens)))
     for b in args.batch:
         for rep in range(args.reps):
-            for wf, qg, kv, (pname, proc) in ((wf, qg, kv, pr) for wf in models
-                                              for qg in (args.quantized_gemm if wf != "bf16" else ["dequant"])
-                                              for kv in args.kv for pr in procs):
+            for wf, qg, kv, (pname, proc), min_p in ((wf, qg, kv, pr, mp) for wf in models
+                                                     for qg in (args.quantized_gemm if wf != "bf16" else ["dequant"])
+                                                     for kv in args.kv for pr in procs
+                                                     for mp in dict.fromkeys((0.0, args.min_p))):
                 m = models[wf]
                 if wf != "bf16":
                     m.set_quantized_gemm(qg)
                 m.set_kv_cache_format("fp8_e4m3" if kv == "fp8" else "bf16")
                 r = decode_latency(m, b, args.prompt_len, args.gen_len, steps=args.steps, do_sample=args.sample,
                                    processors=proc,
-                                   sampler=dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature))
+                                   sampler=dict(top_k=args.top_k, top_p=args.top_p, temperature=args.temperature,
+                                                min_p=min_p))
                 r["top_k"], r["top_p"], r["temperature"] = args.top_k, args.top_p, args.temperature
                 r["processors"] = pname
+                r["min_p"] = min_p
                 r["model"] = args.model
                 r["mp"] = args.tp_proxy
                 r["weights"] = wf
