@@ -1491,7 +1491,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     return py::make_tuple(r.rc, r.why, r.plan.waves, r.plan.kpg, r.plan.rep);
   }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"));
   m.def("attn_set_q8_waves", [](int64_t w) { jla::attn_set_q8_waves((int)w); },
-        "waves per pair of the fp8-cache decode attention pinned to 1 / 8 (tests, A/B); 0: by shape");
+        "waves per pair of the fp8-cache decode attention pinned to 1 / 8, or 2 / 4: its matrix-core form; 0: by shape");
   // (rc, why, nsplit, ws_floats, tickets) of the same plan: the key splits and what a split launch must be given
   m.def("attn_decode_q8_split_check", [](int64_t b, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap, bool masked) {
     const jla::AttnQ8PlanResult r =

@@ -736,7 +736,7 @@ void attn_set_v5_max_pairs(int n) { g_attn_knobs.v5_max_pairs = n < 0 ? AttnKnob
 void attn_set_v5_fold(int n) { g_attn_knobs.v5_fold = (n == 4 || n == 12) ? n : 0; }
 void attn_set_v6(int mode) { g_attn_knobs.v6_mode = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
 void attn_set_v6_wpp(int wpp) { g_attn_knobs.v6_wpp = (wpp == 1 || wpp == 2 || wpp == 4 || wpp == 8) ? wpp : 0; }
-void attn_set_q8_waves(int waves) { g_attn_knobs.q8_waves = (waves == 1 || waves == 8) ? waves : 0; }
+void attn_set_q8_waves(int waves) { g_attn_knobs.q8_waves = (waves == 1 || waves == 2 || waves == 4 || waves == 8) ? waves : 0; }
 void attn_set_q8_splits(int n) { g_attn_knobs.q8_splits = n > 0 ? n : 0; }
 void attn_set_q8_prefill(int mode) { g_attn_knobs.q8_prefill = (mode == 0 || mode == 1) ? mode : -1; }
 

@@ -39,7 +39,6 @@ __global__ void __launch_bounds__(WPP * 64)
   const int pair = blockIdx.x;
   const int b = pair / Hkv, kvh = pair - b * Hkv;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int c = lane >> 4, j = lane & 15;  // lane group (key / dim quarter), MFMA column (q head)
   char* const vbuf = lds6 + w * AD6_WAVE_LDS;
 
   const int slot = slot_ptr[0];
@@ -59,9 +58,8 @@ __global__ void __launch_bounds__(WPP * 64)
   ::wait_vmcnt<0>();
   ad6_q_ready<REP>(qf, lane);
 
-  const int s_begin = lo >= 0 ? lo / AD6_STEP : 0;
-  const int n_steps = lo < hi ? (hi - 1) / AD6_STEP - s_begin + 1 : 0;
-  const int my_steps = n_steps > w ? (n_steps - w + WPP - 1) / WPP : 0;
+  const Ad6Steps steps = ad6_steps<WPP>(lo, hi, w);
+  const int s_begin = steps.first, my_steps = steps.mine;
   auto issue = [&](int step, u32x4 (&kr)[8], char* vslot) {
     ad6_issue<false, DIAG>((s_begin + step) * AD6_STEP, kr, vslot, kb, vb, T, lane);
   };
@@ -104,63 +102,8 @@ __global__ void __launch_bounds__(WPP * 64)
   }
 
   ad6_finish(st);
-  const float m_run = st.m, l_run = st.l;
-  f32x4 (&o)[8] = st.o;
-  // lane (c, j) holds O[head j][dims 16dt + 4c + r]
-  if constexpr (WPP == 1) {
-    if (j < REP) {
-      const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
-      bf16_t* orow = out + ((size_t)b * H + h0 + j) * AD6_DH;
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt) {
-        const u32x2 v = {pack2bf(o[dt][0] * inv, o[dt][1] * inv), pack2bf(o[dt][2] * inv, o[dt][3] * inv)};
-        const int d = 16 * dt + 4 * c;
-        *reinterpret_cast<u32x2*>(orow + d) = v;
-        if (out_pack)
-          *reinterpret_cast<u32x2*>(out_pack + pack_off(b, (h0 + j) * AD6_DH + d, H * AD6_DH)) = v;
-      }
-    }
-  } else {
-    // merge the WPP waves through LDS (the V slots are free once every wave is past its loop)
-    __syncthreads();
-    float* sm_o = reinterpret_cast<float*>(lds6);               // [WPP][REP][128]
-    float* sm_ml = sm_o + WPP * REP * AD6_DH;                    // [WPP][REP][2]
-    if (j < REP) {
-#pragma unroll
-      for (int dt = 0; dt < 8; ++dt)
-        *reinterpret_cast<f32x4*>(sm_o + (w * REP + j) * AD6_DH + 16 * dt + 4 * c) = o[dt];
-      if (c == 0) {
-        sm_ml[(w * REP + j) * 2] = m_run;
-        sm_ml[(w * REP + j) * 2 + 1] = l_run;
-      }
-    }
-    __syncthreads();
-    // REP x 16 chunks of 8 dims
-    for (int t = threadIdx.x; t < REP * 16; t += WPP * 64) {
-      const int h = t >> 4, d0 = 8 * (t & 15);
-      float M = -INFINITY;
-#pragma unroll
-      for (int ww = 0; ww < WPP; ++ww) M = fmaxf(M, sm_ml[(ww * REP + h) * 2]);
-      float num[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, den = 0.f;
-      if (M != -INFINITY) {
-#pragma unroll
-        for (int ww = 0; ww < WPP; ++ww) {
-          const float mw = sm_ml[(ww * REP + h) * 2];
-          const float f = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
-          den += f * sm_ml[(ww * REP + h) * 2 + 1];
-          const float* src = sm_o + (ww * REP + h) * AD6_DH + d0;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) num[e] += f * src[e];
-        }
-      }
-      const float inv = den > 0.f ? 1.f / den : 0.f;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) num[e] *= inv;
-      const u32x4 v = pack8(num);
-      *reinterpret_cast<u32x4*>(out + ((size_t)b * H + h0 + h) * AD6_DH + d0) = v;
-      if (out_pack) *reinterpret_cast<u32x4*>(out_pack + pack_off(b, (h0 + h) * AD6_DH + d0, H * AD6_DH)) = v;
-    }
-  }
+  // one wave writes its heads; more merge through LDS (the V slots are free once every wave is past its loop)
+  ad6_write_out<REP, WPP>(st, lds6, out, out_pack, b, H, h0, w, lane);
 }
 
 static int g_v6_diag = 0;

@@ -87,6 +87,17 @@ JLA_DEV void ad6_q_ready(u32x4 (&qf)[4], int lane) {  // after the wait that ret
   }
 }
 
+// wave w's share of the 32-key steps that hold the keys [lo, hi): steps w, w + WPP, ... counted from first, the step of lo
+struct Ad6Steps {
+  int first, mine;
+};
+template <int WPP>
+JLA_DEV Ad6Steps ad6_steps(int lo, int hi, int w) {
+  const int s_begin = lo >= 0 ? lo / AD6_STEP : 0;
+  const int n_steps = lo < hi ? (hi - 1) / AD6_STEP - s_begin + 1 : 0;
+  return {s_begin, n_steps > w ? (n_steps - w + WPP - 1) / WPP : 0};
+}
+
 // issue one 32-key step starting at key0 (rows clamped to T - 1): V rows into vslot by LDS-DMA (1 KiB block bi = rows
 // 4bi .. 4bi+3, lane L -> row 4bi + L / 16, slot L % 16 <- source chunk slot ^ swz(row)), K rows into kr by asm loads
 // (key l & 15 of block kk, bytes 64jj + 16c). 16 vector-memory ops; the caller counts the waits. SC1: agent-coherent.
@@ -195,6 +206,70 @@ JLA_DEV void ad6_finish(Ad6Acc& st) {
   for (int dt = 0; dt < 8; ++dt) st.o[dt] = ad6_take(st.o[dt]);
   st.l += __shfl_xor(st.l, 16, 64);
   st.l += __shfl_xor(st.l, 32, 64);
+}
+
+// The output of one pair after ad6_finish, by the whole workgroup (w = threadIdx.x >> 6): one wave writes its heads
+// directly; WPP waves merge (m, l, O) once through LDS. lds: the workgroup's buffer, free once every wave is past its
+// loop, at least WPP * REP * (128 + 2) floats. out_pack (or null): the packed copy beside the row-major one.
+template <int REP, int WPP>
+JLA_DEV void ad6_write_out(Ad6Acc& st, char* lds, bf16_t* out, bf16_t* out_pack, int b, int H, int h0, int w, int lane) {
+  const int c = lane >> 4, j = lane & 15;
+  const float m_run = st.m, l_run = st.l;
+  f32x4 (&o)[8] = st.o;
+  // lane (c, j) holds O[head j][dims 16dt + 4c + r]
+  if constexpr (WPP == 1) {
+    if (j < REP) {
+      const float inv = l_run > 0.f ? 1.f / l_run : 0.f;
+      bf16_t* orow = out + ((size_t)b * H + h0 + j) * AD6_DH;
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt) {
+        const u32x2 v = {pack2bf(o[dt][0] * inv, o[dt][1] * inv), pack2bf(o[dt][2] * inv, o[dt][3] * inv)};
+        const int d = 16 * dt + 4 * c;
+        *reinterpret_cast<u32x2*>(orow + d) = v;
+        if (out_pack)
+          *reinterpret_cast<u32x2*>(out_pack + pack_off(b, (h0 + j) * AD6_DH + d, H * AD6_DH)) = v;
+      }
+    }
+  } else {
+    __syncthreads();
+    float* sm_o = reinterpret_cast<float*>(lds);                 // [WPP][REP][128]
+    float* sm_ml = sm_o + WPP * REP * AD6_DH;                    // [WPP][REP][2]
+    if (j < REP) {
+#pragma unroll
+      for (int dt = 0; dt < 8; ++dt)
+        *reinterpret_cast<f32x4*>(sm_o + (w * REP + j) * AD6_DH + 16 * dt + 4 * c) = o[dt];
+      if (c == 0) {
+        sm_ml[(w * REP + j) * 2] = m_run;
+        sm_ml[(w * REP + j) * 2 + 1] = l_run;
+      }
+    }
+    __syncthreads();
+    // REP x 16 chunks of 8 dims
+    for (int t = threadIdx.x; t < REP * 16; t += WPP * 64) {
+      const int h = t >> 4, d0 = 8 * (t & 15);
+      float M = -INFINITY;
+#pragma unroll
+      for (int ww = 0; ww < WPP; ++ww) M = fmaxf(M, sm_ml[(ww * REP + h) * 2]);
+      float num[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, den = 0.f;
+      if (M != -INFINITY) {
+#pragma unroll
+        for (int ww = 0; ww < WPP; ++ww) {
+          const float mw = sm_ml[(ww * REP + h) * 2];
+          const float f = mw == -INFINITY ? 0.f : __builtin_amdgcn_exp2f(mw - M);
+          den += f * sm_ml[(ww * REP + h) * 2 + 1];
+          const float* src = sm_o + (ww * REP + h) * AD6_DH + d0;
+#pragma unroll
+          for (int e = 0; e < 8; ++e) num[e] += f * src[e];
+        }
+      }
+      const float inv = den > 0.f ? 1.f / den : 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) num[e] *= inv;
+      const u32x4 v = pack8(num);
+      *reinterpret_cast<u32x4*>(out + ((size_t)b * H + h0 + h) * AD6_DH + d0) = v;
+      if (out_pack) *reinterpret_cast<u32x4*>(out_pack + pack_off(b, (h0 + h) * AD6_DH + d0, H * AD6_DH)) = v;
+    }
+  }
 }
 
 }  // namespace jla

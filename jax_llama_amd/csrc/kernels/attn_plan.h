@@ -29,7 +29,7 @@ struct AttnKnobs {
   int waves_target = 2048;  // v2 splits the keys until pairs x splits reaches this many waves
   bool v4 = true;           // the register-ring stream (v4); impl 4 turns it off (v2 everywhere v4 would run)
   bool v2_kpg4 = false;     // impl 4: v2's (KPG 4, 2 slots) ring at rep <= 4 for every size, not only from 16384 pairs
-  int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8; 0 = by shape
+  int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8 (VALU forms) or 2 / 4 (the matrix-core form); 0 = by shape
   int q8_splits = 0;        // ... its key splits per pair: 0 = by shape, 1 = never, n > 1 pinned (clamped to the chunks of t_cap)
   int q8_prefill = -1;      // S > 1 on the fp8 KV cache (attn_prefill_q8_plan): -1 = by shape, 0 = always dequantise, 1 = always direct
 };
@@ -164,15 +164,17 @@ inline AttnPlanResult attn_decode_plan(const AttnKnobs& k, int B, int H, int Hkv
 
 // ---- the FP8 (e4m3) KV cache (kv8.hip): one kernel template, attn_decode_q8_kernel, straight on the fp8 bytes: one
 // workgroup per (row, kv head) pair, or -- few pairs with a long context -- one per (pair, key split) with a
-// last-arriver merge; no packed copy. Every rule of that launch:
+// last-arriver merge; no packed copy. Opt-in beside it, attn_decode_q8_mma_kernel: the same bytes on the matrix cores.
+// Every rule of that launch:
 constexpr int ATTN_Q8_ONE_WAVE_MIN_PAIRS = 2048;  // one wave per pair from here (B = 256 at 8 kv heads); see the rule
 constexpr int ATTN_Q8_SPLIT_WGS = 256;            // key splits until pairs x splits reaches this many workgroups ...
 constexpr int ATTN_Q8_SPLIT_MIN_CHUNKS = 4;       // ... of at least this many chunks of t_cap each; see the rule
 constexpr int ATTN_Q8_MAX_SPLITS = 64;            // what a pinned count is cut to (the merge is one workgroup's)
 struct AttnQ8Plan {
   int rep;     // query heads per kv head
-  int waves;   // waves per pair: 8 (v3's structure) or 1 (large batches, as v4 serves them for bf16)
-  int kpg;     // key rows per lane group per chunk
+  int waves;   // waves per pair: 8 (v3's structure) or 1 (large batches, as v4 serves them for bf16); 2 / 4, only when
+               // pinned: the matrix-core form (attn_decode_q8_mma_kernel, v6's structure at that many waves)
+  int kpg;     // key rows per lane group per chunk (0 for the matrix-core form, v6's convention)
   int nsplit;  // key splits per pair (1: the unsplit launch, no workspace); only with 8 waves
   size_t ws_floats;  // nsplit > 1: the launch is given this many floats, [m, l, 0, 0, o[128]] per head and split ...
   int tickets;       // ... and this many zero-initialised int32 tickets, one per pair (self-resetting); 0 / 0 unsplit
@@ -223,7 +225,8 @@ inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, in
   if (H < 1 || Hkv < 1 || H % Hkv) return fail("GQA: H a positive multiple of Hkv");
   const int rep = H / Hkv, pairs = B * Hkv;
   if (rep > 8 || (rep & (rep - 1))) return fail("fp8 KV cache: query heads per kv head 1, 2, 4 or 8");
-  if (k.q8_splits > 1 && k.q8_waves == 1) return fail("fp8 KV cache: key splits (q8_splits > 1) only with 8 waves per pair");
+  if (k.q8_splits > 1 && k.q8_waves != 0 && k.q8_waves != 8)
+    return fail("fp8 KV cache: key splits (q8_splits > 1) only with 8 waves per pair");
   AttnQ8Plan p{};
   p.rep = rep, p.nsplit = 1;
   // One wave per pair from 2048 pairs, 8 waves below. The rule started as the bf16 plan's v3 / v4 boundary (1 wave where
@@ -236,6 +239,10 @@ inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, in
   // so 512 and 1024 pairs (where the old rule ran 1 wave at rep 4) stay with 8 waves, and rep 8 at 2048 pairs (where it
   // ran 8) takes 1. Few pairs with a long context want the 8 waves all the more, and key splits (below).
   p.waves = k.q8_waves ? k.q8_waves : (pairs >= ATTN_Q8_ONE_WAVE_MIN_PAIRS ? 1 : 8);
+  // ---- the matrix-core form, only where q8_waves pins 2 / 4 waves (no shape takes it by default: the pinned-plan tests
+  // hold the rules above, and profiles/kv8_attn_decode_mma_ab.jsonl says where a later rule could): one workgroup per
+  // pair, no key splits, no workspace
+  if (p.waves == 2 || p.waves == 4) return {0, "", p};
   // 16 scores per query-head set and lane group at most (rep x KPG <= 16, the v3 bound: no spills), 8 rows at most
   p.kpg = rep <= 2 ? 8 : 16 / rep;
   // ---- key splits, 8 waves only (the 1-wave form is for pairs that fill the chip on their own). An unsplit pair

@@ -1,5 +1,5 @@
 // The FP8 (OCP e4m3fn) KV cache: the quantising RoPE + cache write, the dequantiser the S > 1 attention reads through,
-// and the decode attention that streams the fp8 bytes.
+// and the decode attentions that stream the fp8 bytes (per-lane dot products; opt-in, on the matrix cores).
 //
 // A KV row is the 128 values of one (batch row, kv head, slot), of K (post-RoPE) or of V. It is stored as 128 e4m3
 // bytes in natural element order plus one fp32 scale 2^e, by the rule of ops/reference.py quantize_fp8_rows: amax =
@@ -8,8 +8,11 @@
 // is the bf16 model whose K / V rows are replaced by q * 2^e when they are written. 132 bytes per row instead of 256.
 // gfx950's FP8 conversions are OCP (e4m3fn), not fnuz.
 #include "attn_merge.h"
+#include "attn_mma.h"
 #include "common.h"
 #include "launchers.h"
+#include "ring.h"
+#include "wq_cvt.h"
 
 namespace jla {
 
@@ -357,8 +360,167 @@ __global__ void __launch_bounds__(WAVES * 64)
   }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Decode attention on the fp8 bytes on the matrix cores (the plan's waves 2 / 4; opt-in, attn_set_q8_waves): v6's math
+// (attn_mma.h: the REP q heads of a pair are the 16 columns of a v_mfma_f32_16x16x32_bf16 tile) on fragments converted in
+// registers. The K fragments and the V image hold exactly q * scale (v_cvt_scalef32_pk_bf16_fp8 with the row's
+// power-of-two scale as the scale operand; bytes 0 with scale 0 give 0), and the step split, scores, online softmax,
+// P.V, wave merge and epilogue are v6's own functions, so the output has the bits v6 writes at the same waves per pair
+// on a bf16 cache that holds the dequantised rows.
+//
+// Work split: v6's. One workgroup per (row, kv head) pair, wave w takes 32-key steps w, w + WPP, ... of [kv_start,
+// slot], one LDS merge at the end; no key splits, no packed copy. Per step and wave, 18 vector-memory ops, all into
+// registers (an LDS-DMA cannot convert):
+//   K  lane (key l & 15, group c = l >> 4) holds dims 32j + 8c .. +7 of its key for dk step j, as in v6: on fp8 rows
+//      one 8-byte load per fragment (4 per key, one address and instruction offsets 0 / 32 / 64 / 96) plus the key's
+//      scale. v6's dim order is kept -- a 16-byte load over two dk steps would move dims between MFMAs, a different
+//      sum -- so the four lanes of a key read 32 contiguous bytes per load. Four conversions per fragment between the
+//      wait and its MFMAs.
+//   V  four 16-byte loads cover the step's 32 x 128 bytes, 1 KiB contiguous each: in load i the eight lanes rr = l >> 3
+//      read row 8i + (rr >> 1) + 4 (rr & 1), 16 dims each, plus the row's scale. Eight conversions per load, then two
+//      ds_write_b128 into v6's row-major bf16 image (ad6_off): 16 consecutive lanes hold rows r and r + 4, whose
+//      swizzles differ in the chunk parity, so they cover all 64 banks once. ad6_compute reads V^T from the image with
+//      ds_read_b64_tr_b16 as in v6. The scale never moves onto P.
+// The ring is v6's two-slot ring with both slots in registers (38 per slot: 16 K, 16 V, 6 scales; v6: 32 K), issued one
+// step ahead as inline asm with one counted vmcnt per step and no branch around the loads. The image is a single 8 KiB
+// slot per wave (half of v6's LDS): it is written after the step's wait and read in the same step, and a wave's LDS
+// operations complete in order, so the image writes need no wait beyond the ones hipcc counts for the reads, and the
+// next step's writes cannot pass this step's reads.
+constexpr int ADQ_NV = 18;  // vector-memory ops per step: 4 V + 4 V scales + 8 K + 2 K scales
+
+struct Adq8Slot {  // one step in registers
+  u32x4 v[4];
+  unsigned vs[4];
+  u32x2 k[8];
+  unsigned ks[2];
+};
+// the V row of this lane in each of the four loads (0..7; + 8 i), and its 16-byte piece
+JLA_DEV int adq8_vrow(int lane) { return ((lane >> 4) & 3) + 4 * ((lane >> 3) & 1); }
+
+// issue the step at key0 (rows clamped to T - 1, as v6); the caller counts the waits
+JLA_DEV void adq8_issue(int key0, Adq8Slot& r, const uint8_t* kb, const float* ksb, const uint8_t* vb, const float* vsb,
+                        int T, int lane) {
+  const int vrow = adq8_vrow(lane), pc = lane & 7;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int key = min(key0 + 8 * i + vrow, T - 1);
+    asm_load<true>(r.v[i], vb + (size_t)key * KV8_DH + 16 * pc);
+    asm_load_b32<true>(r.vs[i], vsb + key);
+  }
+  const int c = lane >> 4, j = lane & 15;
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) {
+    const int key = min(key0 + 16 * kk + j, T - 1);
+    const uint8_t* p = kb + (size_t)key * KV8_DH + 8 * c;
+    asm_load_b64_at<0>(r.k[4 * kk], p);
+    asm_load_b64_at<32>(r.k[4 * kk + 1], p);
+    asm_load_b64_at<64>(r.k[4 * kk + 2], p);
+    asm_load_b64_at<96>(r.k[4 * kk + 3], p);
+    asm_load_b32<true>(r.ks[kk], ksb + key);
+  }
+}
+
+// after the wait that retired the slot's loads: the V image (q * scale as bf16, v6's layout) and the K fragments
+JLA_DEV void adq8_convert(Adq8Slot& r, u32x4 (&kr)[8], char* img, int lane) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    pin(r.v[i]);
+    pin(r.vs[i]);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) pin(r.k[i]);
+  pin(r.ks[0]);
+  pin(r.ks[1]);
+  const int vrow = adq8_vrow(lane), pc = lane & 7;
+  typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int row = 8 * i + vrow;
+    const float sc = __uint_as_float(r.vs[i]);
+    *(lds_u32x4*)(img + ad6_off(row, 2 * pc)) = fp8x8_to_bf16(r.v[i][0], r.v[i][1], sc);
+    *(lds_u32x4*)(img + ad6_off(row, 2 * pc + 1)) = fp8x8_to_bf16(r.v[i][2], r.v[i][3], sc);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) kr[i] = fp8x8_to_bf16(r.k[i][0], r.k[i][1], __uint_as_float(r.ks[i >> 2]));
+}
+
+template <int REP, int WPP>
+__global__ void __launch_bounds__(WPP * 64)
+    attn_decode_q8_mma_kernel(const bf16_t* __restrict__ q, const uint8_t* __restrict__ kq,
+                              const float* __restrict__ ks, const uint8_t* __restrict__ vq,
+                              const float* __restrict__ vs, const int32_t* __restrict__ slot_ptr,
+                              const int32_t* __restrict__ kv_start, const uint8_t* __restrict__ key_mask, int mask_len,
+                              bf16_t* __restrict__ out, int H, int Hkv, int T, int t_cap, float scale_log2) {
+  static_assert(REP >= 1 && REP <= 8 && (WPP == 2 || WPP == 4), "the plan's matrix-core shapes");
+  static_assert(REP * (AD6_DH + 2) * 4 <= AD6_SLOT_BYTES, "the wave merge fits the image slots");
+  extern __shared__ __attribute__((aligned(16))) char ldsq[];
+  const int pair = blockIdx.x;
+  const int b = pair / Hkv, kvh = pair - b * Hkv;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  char* const img = ldsq + w * AD6_SLOT_BYTES;
+
+  const int slot = slot_ptr[0];
+  if (slot >= T && threadIdx.x == 0) JLA_FLAG(JLA_BOUNDS_ATTN_T);
+  const int lo = kv_start[b];
+  const int hi = min(slot + 1, t_cap);  // keys [lo, hi); t_cap <= T (the launcher's check)
+  const uint8_t* mrow = key_mask ? key_mask + (size_t)b * mask_len : nullptr;
+  const int h0 = kvh * REP;
+  const size_t pair_row = ((size_t)b * Hkv + kvh) * (size_t)T;
+  const uint8_t* const kb = kq + pair_row * KV8_DH;
+  const uint8_t* const vb = vq + pair_row * KV8_DH;
+  const float* const ksb = ks + pair_row;
+  const float* const vsb = vs + pair_row;
+
+  // Q^T fragments, and a wait hipcc sees (as in v6: otherwise its vmcnt(0) for these loads lands inside the loop)
+  u32x4 qf[4];
+  ad6_load_q<REP, false>(qf, q + ((size_t)b * H + h0) * AD6_DH, lane);
+  ::wait_vmcnt<0>();
+  ad6_q_ready<REP>(qf, lane);
+
+  const Ad6Steps steps = ad6_steps<WPP>(lo, hi, w);
+  const int my_steps = steps.mine, last = my_steps - 1;
+  auto key_of = [&](int i) { return (steps.first + w + min(i, last) * WPP) * AD6_STEP; };
+  auto issue = [&](int i, Adq8Slot& r) { adq8_issue(key_of(i), r, kb, ksb, vb, vsb, T, lane); };
+  Ad6Acc st;
+  ad6_init(st);
+  // valid = false: a ring slot loaded past the wave's last step (clamped addresses, fully masked, adds nothing)
+  auto compute = [&](int i, bool valid, Adq8Slot& r) {
+    u32x4 kr[8];
+    adq8_convert(r, kr, img, lane);
+    ad6_compute<REP>(st, kr, qf, img, key_of(i), valid, lo, hi, mrow, mask_len, scale_log2, lane);
+  };
+
+  // v6's two-slot ring, branch-free around the loads (see there): every half-iteration issues the next step -- clamped
+  // to the wave's last step past the end, computed fully masked -- and waits for the current one with a counted vmcnt
+  Adq8Slot ra, rb;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    ra.v[i] = rb.v[i] = u32x4{0u, 0u, 0u, 0u};
+    ra.vs[i] = rb.vs[i] = 0u;
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ra.k[i] = rb.k[i] = u32x2{0u, 0u};
+  ra.ks[0] = ra.ks[1] = rb.ks[0] = rb.ks[1] = 0u;
+  if (my_steps > 0) {
+    issue(0, ra);
+    for (int i = 0; i < my_steps; i += 2) {
+      issue(i + 1, rb);
+      wait_vmcnt<ADQ_NV>();  // step i (slot a) landed; step i + 1 stays in flight
+      compute(i, true, ra);
+      issue(i + 2, ra);
+      wait_vmcnt<ADQ_NV>();
+      compute(i + 1, i + 1 < my_steps, rb);
+    }
+    wait_vmcnt<0>();  // the last refill of slot a: drained before the wave ends
+  }
+
+  ad6_finish(st);
+  // the waves merge through LDS (the images are free once every wave is past its loop)
+  ad6_write_out<REP, WPP>(st, ldsq, out, nullptr, b, H, h0, w, lane);
+}
+
 // Launches what attn_decode_q8_plan() (attn_plan.h) names: one instantiation per (rep, kpg, waves, split or not) the plan
-// can give. ws / tickets: needed (and checked against the plan, -2) only where the plan splits the keys.
+// can give, and per (rep, waves) of the matrix-core form. ws / tickets: needed (and checked against the plan, -2) only where the plan splits the keys.
 int attn_decode_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const uint8_t* vq, const float* vs,
                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
                    int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws, size_t ws_floats,
@@ -371,6 +533,21 @@ int attn_decode_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const ui
   const bool split = p.nsplit > 1;
   if (split && Hkv > 65535) return -1;  // (the split grid has the kv heads in y)
   if (split && (!ws || !tickets || ws_floats < p.ws_floats || n_tickets < p.tickets)) return -2;
+  if (p.waves == 2 || p.waves == 4) {  // the matrix-core form: one workgroup per pair, v6's grid and scale
+    if ((long long)B * Hkv > 0x7fffffffLL || T < 1) return -1;
+    const float scale_log2 = 1.4426950408889634f / sqrtf((float)AD6_DH);
+#define JLA_ADQ8M(R, W)                                                                                             \
+  if (p.rep == R && p.waves == W) {                                                                                 \
+    attn_decode_q8_mma_kernel<R, W><<<B * Hkv, W * 64, W * AD6_SLOT_BYTES, s>>>(                                    \
+        q, kq, ks, vq, vs, slot, kv_start, key_mask, mask_len, out, H, Hkv, T, t_cap, scale_log2);                  \
+    JLA_CHECK_LAUNCH();                                                                                             \
+    return 0;                                                                                                       \
+  }
+    JLA_ADQ8M(1, 2) JLA_ADQ8M(2, 2) JLA_ADQ8M(4, 2) JLA_ADQ8M(8, 2)
+    JLA_ADQ8M(1, 4) JLA_ADQ8M(2, 4) JLA_ADQ8M(4, 4) JLA_ADQ8M(8, 4)
+#undef JLA_ADQ8M
+    return -1;
+  }
   const float scale = 1.f / sqrtf((float)Dh);
   const dim3 grid = split ? dim3(p.nsplit, Hkv, B) : dim3(Hkv, B);
 #define JLA_ADQ8(R, K, W, S)                                                                                        \

@@ -164,7 +164,7 @@ void attn_set_v5_max_pairs(int n);  // < 0: the default
 void attn_set_v5_fold(int n);
 void attn_set_v6(int mode);
 void attn_set_v6_wpp(int wpp);
-void attn_set_q8_waves(int waves);  // the fp8 KV cache's kernel: 1 / 8 waves per pair pinned; 0: by shape
+void attn_set_q8_waves(int waves);  // the fp8 KV cache: 1 / 8 waves per pair pinned, 2 / 4: the matrix-core form; 0: by shape
 void attn_set_q8_splits(int n);     // ... its key splits per pair: 0 by shape, 1 never, n > 1 pinned (the plan clamps it)
 void attn_set_q8_prefill(int mode);  // S > 1 on an fp8 cache: -1 by attn_prefill_q8_plan, 0 always dequantise, 1 always direct
 void attn_set_diag(int d);     // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)

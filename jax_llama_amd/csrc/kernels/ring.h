@@ -51,6 +51,12 @@ JLA_DEV void asm_load_b32(unsigned& r, const void* p) {
   else
     r = *reinterpret_cast<const unsigned*>(p);
 }
+// 8 bytes per lane at p + OFF, the offset in the instruction: one address register pair serves all the loads of a row
+// (the fp8 KV cache's K fragments, kv8.hip)
+template <int OFF>
+JLA_DEV void asm_load_b64_at(u32x2& r, const void* p) {
+  asm volatile("global_load_dwordx2 %0, %1, off offset:%2" : "+v"(r) : "v"(p), "i"(OFF) : "memory");
+}
 // agent-coherent (sc1) load: bypasses the caches that can hold a stale copy of a line another
 // workgroup of the same launch wrote write-through (in-launch hand-offs, Guideline 16 R1)
 JLA_DEV void asm_load_sc1(u32x4& r, const void* p) {

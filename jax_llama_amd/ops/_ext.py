@@ -28,6 +28,9 @@ def _load():
         if os.environ.get("JLA_ATTN_IMPL"):
             impl, _, tgt = os.environ["JLA_ATTN_IMPL"].partition(":")
             _EXT.attn_set_impl(int(impl), int(tgt or 0))
+        # JLA_ATTN_Q8_WAVES (default 0: by shape): the fp8 KV cache's decode attention pinned to 1 / 8 waves per pair,
+        # or to its matrix-core form at 2 / 4 (csrc/kernels/attn_plan.h attn_decode_q8_plan; attn_set_q8_waves)
+        _EXT.attn_set_q8_waves(int(os.environ.get("JLA_ATTN_Q8_WAVES", "0")))
     except BaseException as e:  # ImportError, OSError (undefined symbol), ...
         _ERR = e
 

@@ -14,7 +14,8 @@ impl (ext.attn_set_impl / attn_set_v3_max_pairs): 2 = default dispatch; 3 = v3 (
 
 --kv fp8: the FP8 (e4m3) KV cache's kernel (csrc/kernels/kv8.hip) on a cache of random codes, beside the bf16 kernels on
 the bf16 cache that holds the same (dequantised) values, alternating in one process; --q8-waves pins its waves per pair
-(0: the plan's choice) and --q8-splits its key splits per pair (0: the plan's choice, 1: never split, n: pinned; the
+(0: the plan's choice; 1 / 8: the per-lane dot-product forms; 2 / 4: the matrix-core form, unsplit whatever --q8-splits
+says) and --q8-splits its key splits per pair (0: the plan's choice, 1: never split, n: pinned; the
 plan's resulting count goes into the record as q8_splits, the pinned value as q8_splits_pin); every (waves, splits)
 combination is one run. Every record carries the median and the minimum over the rounds and GB/s (the valid K / V bytes
 of the format, scales included, over the median).
@@ -62,7 +63,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"])
-    ap.add_argument("--q8-waves", type=int, nargs="+", default=[0], help="fp8: waves per pair pinned (0: by shape)")
+    ap.add_argument("--q8-waves", type=int, nargs="+", default=[0], help="fp8: waves per pair pinned (0: by shape; 2 / 4: the matrix-core form)")
     ap.add_argument("--q8-splits", type=int, nargs="+", default=[0],
                     help="fp8: key splits per pair pinned (0: by shape, 1: never)")
     args = ap.parse_args()
@@ -95,7 +96,8 @@ def main():
         res, first = {}, None
         graphs = {}
         runs = [("bf16", i) for i in args.impls if "bf16" in args.kv]
-        runs += [("fp8", w, n) for w in args.q8_waves for n in args.q8_splits if k8]
+        # (the matrix-core form has no key splits: one run per wave count, whatever --q8-splits lists)
+        runs += [("fp8", w, n) for w in args.q8_waves for n in (args.q8_splits if w not in (2, 4) else [0]) if k8]
 
         def pin(run):
             set_impl(e, run[1] if run[0] == "bf16" else 2)

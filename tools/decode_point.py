@@ -3,6 +3,9 @@
 unit to run under rocprofv3 for a per-kernel breakdown of small-batch decode.
 
   python tools/decode_point.py --model llama3-8b --batch 1 32 --steps 64
+
+JLA_ATTN_Q8_WAVES=1 / 8 / 2 / 4 in the environment pins the form of the fp8 KV cache's decode attention for the whole
+process (2 / 4: the matrix-core form; csrc/kernels/attn_plan.h); the records carry it as `q8_waves`.
 """
 from __future__ import annotations
 
@@ -88,6 +91,7 @@ def main():
                 r["weights"] = wf
                 r["quantized_gemm"] = qg
                 r["kv"] = kv
+                r["q8_waves"] = int(os.environ.get("JLA_ATTN_Q8_WAVES", "0")) if kv == "fp8" else None
                 r["kv_cache_gb"] = round(m.config.num_hidden_layers * 2 * b * m.n_kv_heads *
                                          (args.prompt_len + args.gen_len) *
                                          (m.head_dim + 4 if kv == "fp8" else 2 * m.head_dim) / 1e9, 2)
