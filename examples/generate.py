@@ -36,13 +36,16 @@ WEIGHT_FORMATS = {"fp8": "fp8_e4m3", "mxfp4": "mxfp4"}  # --weights -> LLaMAForC
 
 
 def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int = 2048, weights: str = "bf16",
-         kv_cache: str = "bf16", quantized_gemm: str = "dequant", **model_kwargs) -> LLaMA:
+         kv_cache: str = "bf16", quantized_gemm: str = "dequant", beam_cache: str = "reorder",
+         **model_kwargs) -> LLaMA:
     """Reference ``load`` (jax_example.py:10-31) on the MI355X runtime. ``weights="fp8"`` / ``"mxfp4"``: the layer
     projections are quantised to FP8 e4m3 / MXFP4 after loading (``LLaMAForCausalLM.quantize_weights_``; each rank its
     own shard).
     ``kv_cache="fp8"``: the KV caches hold FP8 e4m3 rows (``LLaMAForCausalLM.set_kv_cache_format``).
     ``quantized_gemm="direct"``: quantised projections stream their bytes at 65 .. 512 rows too
-    (``LLaMAForCausalLM.set_quantized_gemm``)."""
+    (``LLaMAForCausalLM.set_quantized_gemm``).
+    ``beam_cache="indirect"``: beam search moves no cache row, decode attention reads through a per-beam ancestry
+    table (``LLaMAForCausalLM.set_beam_cache``; bf16 KV cache only)."""
     ctx = init_distributed()
     ctx.setup_mesh(tp=ctx.world)
     with open(os.path.join(ckpt_dir, "params.json")) as f:
@@ -58,17 +61,19 @@ def load(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_seq_len: int =
         model.set_quantized_gemm(quantized_gemm)
     if kv_cache == "fp8":
         model.set_kv_cache_format("fp8_e4m3")
+    model.set_beam_cache(beam_cache)
     return LLaMA(None, model, tokenizer, mesh=Mesh(dp=1, mp=ctx.tp_size, rank=ctx.rank))
 
 
 def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int = 256, temperature: float = 0.8,
          top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1,
          repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
-         quantized_gemm: str = "dequant", top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0):
+         quantized_gemm: str = "dequant", top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0,
+         beam_cache: str = "reorder"):
     """Reference ``main`` (jax_example.py:33-40). ``num_beams > 1``: beam search (temperature is then taken as 0).
     Llama-3 (without beam search) stops on any of the tokenizer's ``stop_tokens`` (end of text, end of turn)."""
     generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache,
-                     quantized_gemm=quantized_gemm)
+                     quantized_gemm=quantized_gemm, beam_cache=beam_cache)
     if num_beams > 1:
         temperature = 0.0
     stops = sorted(generator.tokenizer.stop_tokens) if is_llama3 and num_beams == 1 else None
@@ -86,7 +91,7 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
               weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1, repetition_penalty: float = 1.0,
               no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, quantized_gemm: str = "dequant",
-              top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0):
+              top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0, beam_cache: str = "reorder"):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -99,6 +104,7 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
         model.set_quantized_gemm(quantized_gemm)
     if kv_cache == "fp8":
         model.set_kv_cache_format("fp8_e4m3")
+    model.set_beam_cache(beam_cache)
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
                          dtype=torch.int32)
     gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0 and num_beams == 1,
@@ -145,6 +151,9 @@ if __name__ == "__main__":
                     "per 128-value row instead of 256")
     ap.add_argument("--num_beams", type=int, default=1,
                     help="> 1: beam search with that many beams (2..8; no sampling, no tensor parallelism)")
+    ap.add_argument("--beam-cache", choices=["reorder", "indirect"], default="reorder",
+                    help="beam search: copy every beam's cache rows from its parent's each step, or move nothing and "
+                    "read K / V through a per-beam ancestry table (LLaMAForCausalLM.set_beam_cache; bf16 KV cache only)")
     ap.add_argument("--repetition_penalty", type=float, default=1.0,
                     help="logits processor: every token already in a row's history is scaled down once (1.0: off)")
     ap.add_argument("--no_repeat_ngram_size", type=int, default=0,
@@ -155,10 +164,10 @@ if __name__ == "__main__":
     if a.synthetic:
         synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
                   a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k,
-                  a.min_p, a.typical_p)
+                  a.min_p, a.typical_p, a.beam_cache)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
         main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
              a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k,
-             a.min_p, a.typical_p)
+             a.min_p, a.typical_p, a.beam_cache)

@@ -1100,6 +1100,77 @@ void kv_beam_reorder(Tensor t, Tensor beam_idx, Tensor slot, int64_t k) {
   rc(r, "kv_beam_reorder");
 }
 
+// the ancestry table of the indirect beam cache: anc uint8 [B*K, T] contiguous, in place below slot[0]
+void beam_anc_update(Tensor anc, Tensor beam_idx, Tensor slot, int64_t k) {
+  check_gpu(anc, "beam_anc_update table");
+  check_gpu(beam_idx, "beam_idx");
+  check_gpu(slot, "slot");
+  check(anc.scalar_type() == torch::kUInt8 && anc.dim() == 2, "beam_anc_update: table uint8 [B*K, T]");
+  check(beam_idx.scalar_type() == torch::kInt32 && slot.scalar_type() == torch::kInt32 && slot.numel() == 1,
+        "beam_anc_update: int32 beam_idx, slot [1]");
+  check(k >= 2 && k <= 8 && anc.size(0) % k == 0 && beam_idx.numel() == anc.size(0), "beam_anc_update: rows = B * K");
+  check(anc.size(1) >= 1 && anc.size(1) < (1 << 30), "beam_anc_update: 1 <= T < 2^30");
+  const int r = jla::beam_anc_update(ptr<uint8_t>(anc), ptr<int32_t>(beam_idx), ptr<int32_t>(slot), anc.size(0) / k, k,
+                                     anc.size(1), stream());
+  check(r != -2, "beam_anc_update: at most 65535 prompts");
+  rc(r, "beam_anc_update");
+}
+
+// decode attention through the ancestry table (kernels/attn_decode_anc.hip): bf16 caches [B*K, Hkv, T, 128]
+void attn_decode_anc(Tensor q, Tensor k_cache, Tensor v_cache, Tensor anc, int64_t num_beams, Tensor slot,
+                     Tensor kv_start, c10::optional<Tensor> key_mask, Tensor out, int64_t t_cap,
+                     c10::optional<Tensor> ws, c10::optional<Tensor> tickets) {
+  for (auto* t : {&q, &k_cache, &v_cache, &anc, &slot, &kv_start, &out}) check_gpu(*t, "attn_decode_anc arg");
+  check(q.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16 && q.dim() == 4 && q.size(1) == 1,
+        "attn_decode_anc: q bf16 [B, 1, H, Dh]");
+  const int64_t b = q.size(0), h = q.size(2), dh = q.size(3);
+  check(k_cache.scalar_type() == torch::kBFloat16 && v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 &&
+            k_cache.sizes() == v_cache.sizes() && k_cache.size(0) == b && k_cache.size(3) == dh,
+        "attn_decode_anc: caches bf16 [B, Hkv, T, Dh]");
+  const int64_t hkv = k_cache.size(1), T = k_cache.size(2);
+  check(anc.scalar_type() == torch::kUInt8 && anc.dim() == 2 && anc.size(0) == b && anc.size(1) == T,
+        "attn_decode_anc: table uint8 [B, T]");
+  check(T >= 8 && T < (1 << 30), "attn_decode_anc: 8 <= T < 2^30");
+  check(slot.scalar_type() == torch::kInt32 && slot.numel() >= 1 && kv_start.scalar_type() == torch::kInt32 &&
+            kv_start.numel() == b,
+        "slot/kv_start");
+  check(out.numel() == q.numel(), "attention out shape");
+  check(t_cap >= 0 && t_cap <= T, "t_cap exceeds the cache length");
+  check(b <= 65535 && hkv <= 65535, "attn_decode_anc: at most 65535 rows and kv heads");
+  if (key_mask.has_value()) {
+    check_gpu(*key_mask, "key_mask");
+    check(key_mask->scalar_type() == torch::kUInt8 && key_mask->dim() == 2 && key_mask->size(0) == b,
+          "key_mask must be uint8 [B, L]");
+  }
+  const jla::AttnAncPlanResult r =
+      jla::attn_decode_anc_plan(jla::attn_knobs(), b, h, hkv, dh, t_cap, key_mask.has_value(), num_beams);
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: attn_decode_anc: no plan (", r.why, "; see attn_plan.h)");
+  float* wsp = nullptr;
+  int32_t* tkp = nullptr;
+  if (r.plan.nsplit > 1) {
+    TORCH_CHECK(ws.has_value() && tickets.has_value(), "jax_llama_amd._C: attn_decode_anc: the plan splits the keys (nsplit ",
+                r.plan.nsplit, "): ws and tickets are required (attn_decode_anc_plan_check)");
+    check_gpu(*ws, "ws");
+    check_gpu(*tickets, "tickets");
+    TORCH_CHECK(ws->scalar_type() == torch::kFloat32 && ws->device() == q.device() &&
+                    (size_t)ws->numel() >= r.plan.ws_floats,
+                "jax_llama_amd._C: attn_decode_anc: ws must be fp32 on q's device with at least B * H * nsplit * (128 + 4) = ",
+                r.plan.ws_floats, " floats (attn_decode_anc_plan_check)");
+    TORCH_CHECK(tickets->scalar_type() == torch::kInt32 && tickets->device() == q.device() &&
+                    tickets->numel() >= r.plan.tickets,
+                "jax_llama_amd._C: attn_decode_anc: tickets must be int32 on q's device, one per (row, kv head) pair = ",
+                r.plan.tickets, " (attn_decode_anc_plan_check)");
+    wsp = ptr<float>(*ws);
+    tkp = ptr<int32_t>(*tickets);
+  }
+  const uint8_t* km = key_mask.has_value() ? ptr<uint8_t>(*key_mask) : nullptr;
+  const int ml = key_mask.has_value() ? key_mask->size(1) : 0;
+  rc(jla::attn_decode_anc(cbf(q), cbf(k_cache), cbf(v_cache), ptr<uint8_t>(anc), num_beams, ptr<int32_t>(slot),
+                          ptr<int32_t>(kv_start), km, ml, bf(out), b, h, hkv, dh, T, t_cap, stream(), wsp,
+                          r.plan.ws_floats, tkp, r.plan.tickets),
+     "attn_decode_anc");
+}
+
 // ---- custom all-reduce (allreduce.hip) -------------------------------------------------------
 py::tuple car_alloc(int64_t max_bytes, int64_t world) {
   void* buf = nullptr;
@@ -1421,7 +1492,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     const int r = reset ? 1 : 0;
     return (int64_t)(jla::jla_bounds_norm_embed(r) | jla::jla_bounds_rope_kv(r) | jla::jla_bounds_sample(r) |
                      jla::jla_bounds_gemm(r) | jla::jla_bounds_gemv(r) | jla::jla_bounds_kv8(r) |
-                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r) |
+                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_decode_anc(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r) |
                      jla::jla_bounds_logits_proc(r));
   }, "OR of the bounds-checked debug build's error words (JLA_BOUNDS_* bits); always 0 in a release build",
         py::arg("reset") = false);
@@ -1559,4 +1630,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   m.def("beam_alive", &beam_alive);
   m.def("beam_step", &beam_step);
   m.def("kv_beam_reorder", &kv_beam_reorder);
+  // the indirect beam cache (kernels/attn_decode_anc.hip, beam.hip beam_anc_update)
+  m.def("beam_anc_update", &beam_anc_update, py::arg("anc"), py::arg("beam_idx"), py::arg("slot"), py::arg("k"));
+  m.def("attn_decode_anc", &attn_decode_anc, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("anc"),
+        py::arg("num_beams"), py::arg("slot"), py::arg("kv_start"), py::arg("key_mask").none(true), py::arg("out"),
+        py::arg("t_cap"), py::arg("ws") = py::none(), py::arg("tickets") = py::none());
+  // (rc, why, rep, kpg, nsplit, ws_floats, tickets) of that launch under the current knobs (kernels/attn_plan.h)
+  m.def("attn_decode_anc_plan_check", [](int64_t b, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap, bool masked,
+                                         int64_t num_beams) {
+    const jla::AttnAncPlanResult r = jla::attn_decode_anc_plan(jla::attn_knobs(), (int)b, (int)h, (int)hkv, (int)dh,
+                                                               (int)t_cap, masked, (int)num_beams);
+    return py::make_tuple(r.rc, r.why, r.plan.rep, r.plan.kpg, r.plan.nsplit, (int64_t)r.plan.ws_floats, r.plan.tickets);
+  }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"), py::arg("num_beams"));
+  m.def("attn_set_anc_splits", [](int64_t n) { jla::attn_set_anc_splits((int)n); },
+        "key splits per pair of the beam-ancestry decode attention: 0 by shape, 1 never, n > 1 pinned (tests, A/B)");
 }

@@ -31,6 +31,7 @@ struct AttnKnobs {
   bool v2_kpg4 = false;     // impl 4: v2's (KPG 4, 2 slots) ring at rep <= 4 for every size, not only from 16384 pairs
   int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8 (VALU forms) or 2 / 4 (the matrix-core form); 0 = by shape
   int q8_splits = 0;        // ... its key splits per pair: 0 = by shape, 1 = never, n > 1 pinned (clamped to the chunks of t_cap)
+  int anc_splits = 0;       // the beam-ancestry kernel (attn_decode_anc_plan): key splits per pair, 0 = by shape, 1 = never, n > 1 pinned
   int q8_prefill = -1;      // S > 1 on the fp8 KV cache (attn_prefill_q8_plan): -1 = by shape, 0 = always dequantise, 1 = always direct
 };
 
@@ -276,6 +277,72 @@ inline AttnQ8PlanResult attn_decode_q8_plan(const AttnKnobs& k, int B, int H, in
     } else {
       ns = (ATTN_Q8_SPLIT_WGS + pairs - 1) / pairs;
       most = t_cap / (ATTN_Q8_SPLIT_MIN_CHUNKS * ch);
+    }
+    p.nsplit = ns > most ? (most < 1 ? 1 : most) : ns;
+  }
+  if (p.nsplit > 1) {
+    p.ws_floats = (size_t)B * H * p.nsplit * ATTN_PART_FLOATS;
+    p.tickets = pairs;
+  }
+  return {0, "", p};
+}
+
+// ---- decode attention through a beam-ancestry table (attn_decode_anc.hip): query row b K + j reads key slot t from
+// the physical row b K + anc[b K + j, t] of a bf16 cache that beam search never moves. One kernel template: an 8-wave
+// workgroup per (row, kv head) pair, or per (pair, key split) with a last-arriver merge; no packed copy.
+//
+// Why the VALU structure (v3's, as the fp8 kernel has it) and not v6's matrix-core form. (1) A lane group of 16 lanes
+// is one key row here, so one table byte maps to one group and the KPG bytes of a group's consecutive keys are a single
+// small load; v6's K fragments put 16 keys in the 16 lanes of a group and its V DMA another 8 rows per instruction, so
+// every lane would extract its own byte twice per step, from two different words. (2) Beam shapes are few pairs with
+// long contexts, which need key splits; the wave and key-split merges of attn_merge.h are written for this lane layout
+// (8 dims per lane, (m, l, o) per wave), v6 has its own wave merge and no key splits. (3) The model beam search is run
+// on first is rep 4 (Llama-3-8B), where the VALU forms are not compute-bound. At rep 8 they are (see the v6 rule
+// above), and there this kernel pays for the choice; a matrix-core form at rep 8 is the follow-up, once records say
+// how much.
+constexpr int ATTN_ANC_SPLIT_WGS = 256;       // key splits until pairs x splits reaches this many workgroups ...
+constexpr int ATTN_ANC_SPLIT_MIN_CHUNKS = 4;  // ... of at least this many chunks of t_cap each
+constexpr int ATTN_ANC_MAX_SPLITS = 64;       // what a pinned count is cut to (the merge is one workgroup's)
+constexpr int ATTN_ANC_MAX_BEAMS = 8;         // beam.hip's BEAM_MAX_K
+struct AttnAncPlan {
+  int rep;     // query heads per kv head
+  int kpg;     // consecutive keys per lane group per chunk: 8 / 8 / 4 / 2 at rep 1 / 2 / 4 / 8 (a chunk is 32 kpg keys)
+  int nsplit;  // key splits per pair (1: the unsplit launch, no workspace)
+  size_t ws_floats;  // nsplit > 1: the launch is given this many floats, [m, l, 0, 0, o[128]] per head and split ...
+  int tickets;       // ... and this many zero-initialised int32 tickets, one per pair (self-resetting); 0 / 0 unsplit
+};
+struct AttnAncPlanResult {
+  int rc;           // 0 legal; -1 not
+  const char* why;  // the rule that refused the call
+  AttnAncPlan plan;
+};
+inline AttnAncPlanResult attn_decode_anc_plan(const AttnKnobs& k, int B, int H, int Hkv, int Dh, int t_cap, bool masked,
+                                              int num_beams) {
+  const auto fail = [](const char* why) { return AttnAncPlanResult{-1, why, AttnAncPlan{}}; };
+  (void)masked;  // no rule depends on it (both launch forms take a key mask)
+  if (Dh != ATTN_DH) return fail("head dim: Dh == 128");
+  if (H < 1 || Hkv < 1 || H % Hkv) return fail("GQA: H a positive multiple of Hkv");
+  const int rep = H / Hkv, pairs = B * Hkv;
+  if (rep > 8 || (rep & (rep - 1))) return fail("ancestry table: query heads per kv head 1, 2, 4 or 8");
+  if (num_beams < 1 || num_beams > ATTN_ANC_MAX_BEAMS) return fail("ancestry table: 1 to 8 beams per prompt");
+  if (B > 0 && B % num_beams) return fail("ancestry table: the rows are whole groups of num_beams");
+  AttnAncPlan p{};
+  p.rep = rep, p.nsplit = 1;
+  // 16 scores per query-head set and lane group at most (rep x KPG <= 16, the v3 bound), 8 keys (one 8-byte table
+  // word) at most
+  p.kpg = rep <= 2 ? 8 : 16 / rep;
+  // ---- key splits: the fp8 kernel's rule (one workgroup per CU is the count to aim for, a split shorter than 4 chunks
+  // loses to its merge; its records are in attn_decode_q8_plan) until this kernel has records of its own. A pinned
+  // count is cut so that no split is emptier than one chunk at t_cap.
+  if (B > 0 && k.anc_splits != 1) {
+    const int ch = 32 * p.kpg;
+    int ns, most;
+    if (k.anc_splits > 1) {
+      ns = k.anc_splits < ATTN_ANC_MAX_SPLITS ? k.anc_splits : ATTN_ANC_MAX_SPLITS;
+      most = (t_cap + ch - 1) / ch;
+    } else {
+      ns = (ATTN_ANC_SPLIT_WGS + pairs - 1) / pairs;
+      most = t_cap / (ATTN_ANC_SPLIT_MIN_CHUNKS * ch);
     }
     p.nsplit = ns > most ? (most < 1 ? 1 : most) : ns;
   }

@@ -7,6 +7,7 @@
 //   every source before it stores), and writes beam_idx, the next input tokens, positions + 1, cur_len + 1, slot + 1.
 //   With alive == 0 it writes the identity beam_idx and nothing else.
 // kv_beam_reorder: every beam's KV rows follow its parent, in place, for the slots below the device slot counter.
+// beam_anc_update: the indirect beam cache's step instead of it: the rows stay, a uint8 ancestry table is permuted.
 //
 // Score arithmetic is single fp32 adds and multiplies (contraction off: an fma would round differently from the CPU).
 #include "common.h"
@@ -302,6 +303,109 @@ int kv_beam_reorder(void* base, const int32_t* beam_idx, const int32_t* slot, in
   if (((size_t)T * RB) % 16 == 0 && ((uintptr_t)base) % 16 == 0)
     return kv_beam_reorder_launch<u32x4>(base, beam_idx, slot, layers, groups, K, heads, T, RB, s);
   return kv_beam_reorder_launch<uint32_t>(base, beam_idx, slot, layers, groups, K, heads, T, RB, s);
+}
+
+// ---- ancestry-table update (the indirect beam cache) -------------------------------------------------------------
+// anc uint8 [groups * K, T]: anc[g K + j, t] names the beam of group g whose physical cache row holds key slot t of
+// logical row g K + j (attn_decode_anc.hip reads K / V through it; the cache itself never moves). After a beam step
+// that made beam_idx[g K + j'] the parent of row j' and advanced the slot counter to n:
+//     anc[g K + j', t] = anc_old[g K + beam_idx[g K + j'], t]   for t < n;   columns t >= n untouched.
+// Why the permutation alone is the whole update. The table starts as 0 in the prompt columns [0, S) (every beam reads
+// the prompt from beam 0's row) and as the identity anc[g K + j, t] = j from column S on, and only columns below the
+// counter are ever permuted. The step just taken wrote each row's new key into that row's OWN physical row at slot
+// n - 1, and column n - 1 was still the identity then (it was >= the counter at every earlier update): it already
+// holds the writer's own index. Permuting it with the rest therefore gives the child the parent's row for the newest
+// key as for every older one -- no special case for the newest column. A dead step (alive == 0) leaves the counter and
+// writes the identity beam_idx: nothing changes, so the captured step is safe to replay past the end of the search.
+//
+// kv_beam_reorder's pattern: a thread owns unit u (sizeof(U) = 16 columns, or 1 where T is no multiple of 16) of one
+// group across its K beams, issues the K loads from the permuted sources and then the stores of the rows that changed
+// parent; no other thread touches those addresses. The unit that straddles the counter keeps its bytes at t >= n by a
+// byte-wise select against the row's own old unit. Groups whose beam_idx is the identity return at once.
+template <int K, typename U>
+__global__ void __launch_bounds__(256)
+    beam_anc_update_kernel(U* anc, const int32_t* __restrict__ beam_idx, const int32_t* __restrict__ slot, int T) {
+  const int g = blockIdx.y;
+  int p[K];
+  bool ident = true;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    int v = beam_idx[g * K + j];
+    if (v < 0 || v >= K) {
+      JLA_FLAG(JLA_BOUNDS_BEAM);
+      v = v < 0 ? 0 : K - 1;
+    }
+    p[j] = v;
+    ident = ident && v == j;
+  }
+  if (ident) return;
+  int n = slot[0];
+  if (n < 0 || n > T) {
+    JLA_FLAG(JLA_BOUNDS_KV_SLOT);
+    n = n < 0 ? 0 : T;
+  }
+  constexpr int UB = (int)sizeof(U);
+  const int row = T / UB;  // units per table row (UB divides T: the launcher's choice of U)
+  const int units = (n + UB - 1) / UB;
+  U* grp = anc + (size_t)g * K * row;
+  for (int u = blockIdx.x * 256 + threadIdx.x; u < units; u += gridDim.x * 256) {
+    U v[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) v[j] = grp[(size_t)p[j] * row + u];
+    if constexpr (UB == 16) {
+      const int keep = n - u * UB;  // columns of this unit below the counter (>= 1)
+      if (keep < UB) {              // the straddling unit: bytes at t >= n stay the row's own
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          const U old = grp[(size_t)j * row + u];
+#pragma unroll
+          for (int d = 0; d < 4; ++d) {
+            const int kb = min(max(keep - 4 * d, 0), 4);  // bytes of dword d that move
+            const uint32_t m = kb >= 4 ? 0xffffffffu : ((1u << (8 * kb)) - 1u);
+            v[j][d] = (v[j][d] & m) | (old[d] & ~m);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < K; ++j)
+      if (p[j] != j) grp[(size_t)j * row + u] = v[j];
+  }
+}
+
+template <typename U>
+static int beam_anc_update_launch(uint8_t* anc, const int32_t* beam_idx, const int32_t* slot, int groups, int K, int T,
+                                  hipStream_t s) {
+  const int row = T / (int)sizeof(U);
+  const dim3 grid((unsigned)((row + 255) / 256), (unsigned)groups);
+  U* p = (U*)anc;
+  switch (K) {
+#define JLA_ANC_CASE(KK)                                                          \
+  case KK:                                                                        \
+    beam_anc_update_kernel<KK, U><<<grid, 256, 0, s>>>(p, beam_idx, slot, T);     \
+    break;
+    JLA_ANC_CASE(2)
+    JLA_ANC_CASE(3)
+    JLA_ANC_CASE(4)
+    JLA_ANC_CASE(5)
+    JLA_ANC_CASE(6)
+    JLA_ANC_CASE(7)
+    JLA_ANC_CASE(8)
+#undef JLA_ANC_CASE
+    default:
+      return -1;
+  }
+  JLA_CHECK_LAUNCH();
+  return 0;
+}
+
+int beam_anc_update(uint8_t* anc, const int32_t* beam_idx, const int32_t* slot, int groups, int K, int T,
+                    hipStream_t s) {
+  if (groups <= 0 || T <= 0 || K < 2 || K > BEAM_MAX_K) return -1;
+  if (groups > 65535) return -2;
+  if (T % 16 == 0 && ((uintptr_t)anc) % 16 == 0)
+    return beam_anc_update_launch<u32x4>(anc, beam_idx, slot, groups, K, T, s);
+  return beam_anc_update_launch<uint8_t>(anc, beam_idx, slot, groups, K, T, s);
 }
 
 JLA_BOUNDS_ACCESSOR(beam)

@@ -166,6 +166,7 @@ void attn_set_v6(int mode);
 void attn_set_v6_wpp(int wpp);
 void attn_set_q8_waves(int waves);  // the fp8 KV cache: 1 / 8 waves per pair pinned, 2 / 4: the matrix-core form; 0: by shape
 void attn_set_q8_splits(int n);     // ... its key splits per pair: 0 by shape, 1 never, n > 1 pinned (the plan clamps it)
+void attn_set_anc_splits(int n);    // the beam-ancestry kernel's key splits per pair: 0 by shape, 1 never, n > 1 pinned (the plan clamps it)
 void attn_set_q8_prefill(int mode);  // S > 1 on an fp8 cache: -1 by attn_prefill_q8_plan, 0 always dequantise, 1 always direct
 void attn_set_diag(int d);     // tools only: 1 = v2 / v4 stream K/V without the math (wrong results)
 void attn_set_v6_diag(int d);  // tools only: v6 ablations (1 no compute, 2 no K loads, 4 no V DMAs; wrong results)
@@ -205,6 +206,16 @@ int attn_decode_q8(const bf16_t* q, const uint8_t* kq, const float* ks, const ui
                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
                    int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws = nullptr,
                    size_t ws_floats = 0, int32_t* tickets = nullptr, int n_tickets = 0);
+// ---- decode attention through a beam-ancestry table (attn_decode_anc.hip): bf16 caches [B, Hkv, T, 128] that beam
+// search never moves, anc uint8 [B, T]: row r = g num_beams + j reads key slot t from row g num_beams + min(anc[r, t],
+// num_beams - 1). Launched as attn_decode_anc_plan() (attn_plan.h) says; returns the plan's rc where it refuses, -1 for
+// T < 8. Where the plan splits the keys ws / tickets hold the plan's ws_floats / tickets (tickets zero-initialised
+// once, self-resetting), -2 if they do not; an unsplit launch ignores them.
+unsigned jla_bounds_attn_decode_anc(int reset);
+int attn_decode_anc(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const uint8_t* anc, int num_beams,
+                    const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
+                    int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws = nullptr,
+                    size_t ws_floats = 0, int32_t* tickets = nullptr, int n_tickets = 0);
 void attn_prefill_set_impl(int impl);  // 2 = GQA-shared MFMA 32x32 flash kernel (default), 1 = v1
 int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                  const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,
@@ -279,6 +290,10 @@ int beam_step(const float* cand_v, const int32_t* cand_i, const float* lse, int3
               int K, int L, int S, int eos, int early, hipStream_t s);
 int kv_beam_reorder(void* base, const int32_t* beam_idx, const int32_t* slot, int layers, int groups, int K,
                     int heads, int T, int RB, hipStream_t s);
+// the ancestry table's step (the indirect beam cache): anc uint8 [groups * K, T], in place, columns below slot[0]:
+// anc[g K + j, t] = anc_old[g K + beam_idx[g K + j], t]
+int beam_anc_update(uint8_t* anc, const int32_t* beam_idx, const int32_t* slot, int groups, int K, int T,
+                    hipStream_t s);
 // CU placement (placement.hip): CU-masked streams and a census of where a launch's workgroups run
 int cu_census(uint32_t* out, int blocks, hipStream_t s);
 int cu_mask_stream_create(const uint32_t* mask, int words, hipStream_t* out);

@@ -52,6 +52,10 @@ class KVCache:
         self.max_length = max_length
         self.index = 0  # host mirror of the number of filled slots
         self.index_t = torch.zeros(1, dtype=torch.int32, device=device)
+        # the indirect beam cache (runtime/engine.py BeamEngine): uint8 [batch_size, max_length], row b*K + j reads key
+        # slot t from row b*K + beam_anc[b*K + j, t]; None: every row reads its own slots
+        self.beam_anc = None
+        self.beam_k = 0
 
     @property
     def device(self):

@@ -430,6 +430,27 @@ class LLaMAForCausalLM:
     def kv_cache_format(self) -> str:
         return getattr(self, "_kv_cache_format", "bf16")
 
+    BEAM_CACHE_MODES = ("reorder", "indirect")
+
+    def set_beam_cache(self, mode: str) -> "LLaMAForCausalLM":
+        """How ``generate(num_beams=K)`` keeps the KV cache consistent with the beams: ``"reorder"`` (the default) copies
+        every beam's cache rows from its parent's after each step (``ops.kv_beam_reorder``); ``"indirect"`` moves
+        nothing -- every beam carries an ancestry table that names, per key slot, the beam of its prompt whose row
+        holds that slot, and decode attention reads K / V through it (``ops.attention(beam_anc=...)``; bf16 KV cache
+        only: with the fp8_e4m3 cache the beam engine raises ``ValueError`` when it is built). Both modes return the
+        same hypotheses. Runtime state: not written to checkpoints. ``ValueError`` for an unknown mode. Drops this
+        model's cached decode engines (their graphs captured the other step)."""
+        if mode not in self.BEAM_CACHE_MODES:
+            raise ValueError(f"set_beam_cache: unknown mode {mode!r} (one of {self.BEAM_CACHE_MODES})")
+        self._beam_cache = mode
+        from ..runtime.engine import drop_engines
+        drop_engines(self)
+        return self
+
+    @property
+    def beam_cache(self) -> str:
+        return getattr(self, "_beam_cache", "reorder")
+
     def init_cache(self, batch_size: int, max_length: int, kv_format: Optional[str] = None) -> KVCache:
         """Reference ``init_cache(B, T)`` (``model.py:459-476``) without a dummy forward. ``kv_format``: this cache's
         format (default: the model's, ``set_kv_cache_format``)."""

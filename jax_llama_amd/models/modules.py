@@ -39,14 +39,17 @@ class LLaMAAttention:
                  output_attentions: bool = False, pk: Optional["PackedActs"] = None) -> Optional[torch.Tensor]:
         m, lw = self.model, self.weights
         kc, vc = cache.layer(self.layer_idx)
+        # the indirect beam cache: decode reads K / V through the cache's ancestry table (never on a row view: prefill)
+        anc = getattr(cache, "beam_anc", None) if seq_len == 1 else None
+        nbeams = cache.beam_k if anc is not None else 0
         splits = og = 0
         o_state = None
         if not output_attentions:
             # the o projection in the same launch where it fits (the 70B tensor-parallel shard at small batch)
-            og = ops.qkv_attention_o_groups(hb, lw.o, m.n_heads, m.n_kv_heads, kc) if seq_len == 1 else 0
+            og = ops.qkv_attention_o_groups(hb, lw.o, m.n_heads, m.n_kv_heads, kc, anc) if seq_len == 1 else 0
             o_state = m.comm.fused_o_state(hb, lw.o) if og else None
             og = og if o_state is not None else 0
-            splits = ops.qkv_attention_splits(hb, lw.qkv, kc, seq_len, m.n_heads, m.n_kv_heads, key_mask, og)
+            splits = ops.qkv_attention_splits(hb, lw.qkv, kc, seq_len, m.n_heads, m.n_kv_heads, key_mask, og, anc)
             if og and not splits:
                 og = 0
                 splits = ops.qkv_attention_splits(hb, lw.qkv, kc, seq_len, m.n_heads, m.n_kv_heads, key_mask)
@@ -73,11 +76,13 @@ class LLaMAAttention:
             # reference returns (:277-286) are materialised beside it by the fp32 oracle, on the tensors' device
             s0 = int(slot0) if not torch.is_tensor(slot0) else int(slot0.item())
             kw, vw = (ops.kv8_dequant(kc, vc, s0 + seq_len) if ops.is_fp8_kv(kc) else (kc, vc))  # (an FP8 cache: its rows)
+            if anc is not None:
+                kw, vw = ref.gather_anc(kw, anc, nbeams), ref.gather_anc(vw, anc, nbeams)
             _, weights = ref.attention(q4, kw, vw, s0, kv_start, key_mask, return_weights=True)
-            a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask)
+            a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask, beam_anc=anc, num_beams=nbeams)
         else:
-            att_p = pk.att if pk is not None and ops.attention_packs(q4, kc, key_mask) else None
-            a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask, out_packed=att_p)
+            att_p = pk.att if pk is not None and ops.attention_packs(q4, kc, key_mask, anc) else None
+            a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask, out_packed=att_p, beam_anc=anc, num_beams=nbeams)
         m._row_parallel(a, lw.o, h, hb, x_packed=att_p, mirror_packed=pk.hb if pk else None)
         if pk is not None and pk.hb is not None:
             pk.hb_ok = True

@@ -692,19 +692,23 @@ def _num_cus(device) -> int:
     return _CUS[key]
 
 
-def qkv_attention_o_groups(x: torch.Tensor, w_o, n_heads: int, n_kv_heads: int, k_cache=None) -> int:
+def qkv_attention_o_groups(x: torch.Tensor, w_o, n_heads: int, n_kv_heads: int, k_cache=None, beam_anc=None) -> int:
     """Workgroups of the o projection when the fused decode launch can also run it (``linear_qkv_attention(o=...)``),
-    else 0 (always 0 with an ``Fp8KV`` cache: the fused launch reads and writes bf16 caches only)."""
-    if not QKV_ATTN_O or not _is_gpu(x) or is_quantized(w_o) or is_fp8_kv(k_cache):
+    else 0 (always 0 with an ``Fp8KV`` cache: the fused launch reads and writes bf16 caches only; and with a beam
+    ancestry table, of which it knows nothing)."""
+    if not QKV_ATTN_O or not _is_gpu(x) or is_quantized(w_o) or is_fp8_kv(k_cache) or beam_anc is not None:
         return 0
     return int(ext().qkv_attn_o_groups(x.shape[0], n_heads // n_kv_heads, w_o.n, w_o.k))
 
 
 def qkv_attention_splits(x: torch.Tensor, w, k_cache: torch.Tensor, seq_len: int, n_heads: int, n_kv_heads: int,
-                         key_mask: Optional[torch.Tensor] = None, o_groups: int = 0) -> int:
+                         key_mask: Optional[torch.Tensor] = None, o_groups: int = 0, beam_anc=None) -> int:
     """Attention workgroups per (row, kv head) pair of the fused qkv + attention launch for this decode step, or 0
-    when it does not apply (prefill, a key mask, M > 32, a cache longer than 512, or a grid the CUs cannot hold at
-    once). ``o_groups``: the launch also holds the o projection's workgroups (``qkv_attention_o_groups``)."""
+    when it does not apply (prefill, a key mask, a beam ancestry table, M > 32, a cache longer than 512, or a grid the
+    CUs cannot hold at once). ``o_groups``: the launch also holds the o projection's workgroups
+    (``qkv_attention_o_groups``)."""
+    if beam_anc is not None:
+        return 0  # (the indirect beam cache: the fused launch reads each row's own keys only)
     if not QKV_ATTN or seq_len != 1 or key_mask is not None or not _is_gpu(x) or x.dtype != BF16 or is_quantized(w):
         return 0  # (an Fp8Linear / Mxfp4Linear: the fused launch reads bf16 fragments only)
     if is_fp8_kv(k_cache):
@@ -761,11 +765,12 @@ def linear_qkv_attention(x: torch.Tensor, w, rms_eps: Optional[float], table: to
     return out
 
 
-def attention_packs(q: torch.Tensor, k_cache: torch.Tensor, key_mask: Optional[torch.Tensor] = None) -> bool:
+def attention_packs(q: torch.Tensor, k_cache: torch.Tensor, key_mask: Optional[torch.Tensor] = None,
+                    beam_anc=None) -> bool:
     """Whether ``attention(..., out_packed=...)`` can write the packed copy for this decode shape: the ``packs`` of
     the launch's plan (csrc/kernels/attn_plan.h; it does not depend on how many key slots the launch covers)."""
     bsz, s, h, dh = q.shape
-    if s != 1 or is_fp8_kv(k_cache):  # (the fp8-cache kernel writes no packed copy)
+    if s != 1 or is_fp8_kv(k_cache) or beam_anc is not None:  # (the fp8-cache and ancestry kernels write no packed copy)
         return False
     rc, _why, _kernel, _nsplit, packs, *_ = ext().attn_decode_plan_check(
         bsz, h, k_cache.shape[1], dh, k_cache.shape[2], key_mask is not None)
@@ -774,20 +779,48 @@ def attention_packs(q: torch.Tensor, k_cache: torch.Tensor, key_mask: Optional[t
 
 def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot0, kv_start: torch.Tensor,
               key_mask: Optional[torch.Tensor] = None, max_kv: Optional[int] = None,
-              out_packed: Optional[torch.Tensor] = None) -> torch.Tensor:
+              out_packed: Optional[torch.Tensor] = None, beam_anc: Optional[torch.Tensor] = None,
+              num_beams: int = 0) -> torch.Tensor:
     """Causal/padded attention of ``q [B, S, H, Dh]`` (queries at cache slots slot0+s)
     against ``[B, Hkv, T, Dh]`` caches. Returns ``[B*S, H*Dh]`` bf16.
 
     ``max_kv`` bounds the number of key slots the launch must cover (defaults to the cache
-    length T so the launch shape is static and graph-capturable)."""
+    length T so the launch shape is static and graph-capturable).
+
+    ``beam_anc`` (uint8 ``[B, T]``) with ``num_beams = K``: the indirect beam cache. Row ``r = b*K + j`` reads key
+    slot t from physical row ``b*K + min(beam_anc[r, t], K - 1)`` (``ref.attention_anc``; on the GPU
+    csrc/kernels/attn_decode_anc.hip). Decode only (S = 1), bf16 caches, no packed copy: ``ValueError`` otherwise."""
     bsz, s, h, dh = q.shape
+    if beam_anc is not None:
+        if s != 1 or is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
+            raise ValueError("attention: a beam ancestry table serves decode (S = 1) on a bf16 cache only")
+        if out_packed is not None:
+            raise ValueError("attention: no packed output copy with a beam ancestry table (attention_packs)")
+        if not 1 <= int(num_beams) <= BEAM_MAX or bsz % int(num_beams) or tuple(beam_anc.shape) != (bsz, k_cache.shape[2]):
+            raise ValueError("attention: beam_anc must be uint8 [B, T] with B a multiple of num_beams in [1, 8]")
     if not _is_gpu(q):
         s0 = int(slot0) if not torch.is_tensor(slot0) else int(slot0.item())
+        if beam_anc is not None:
+            return ref.attention_anc(q, k_cache, v_cache, s0, kv_start, beam_anc, int(num_beams),
+                                     key_mask).reshape(bsz * s, h * dh)
         return ref.attention(q, k_cache, v_cache, s0, kv_start, key_mask).reshape(bsz * s, h * dh)
     out = torch.empty(bsz * s, h * dh, dtype=BF16, device=q.device)
     slot_t = _slot_tensor(slot0, q.device)
     t_cap = int(max_kv) if max_kv is not None else k_cache.shape[2]
     e = ext()
+    if beam_anc is not None:
+        # one plan call (csrc/kernels/attn_plan.h attn_decode_anc_plan): few pairs with a long context split the keys,
+        # and that launch needs the partials' workspace and one ticket per pair; a shape the plan refuses is reported
+        # by the launch
+        _rc, _why, _rep, _kpg, nsplit, ws_floats, n_tickets = e.attn_decode_anc_plan_check(
+            bsz, h, k_cache.shape[1], dh, t_cap, key_mask is not None, int(num_beams))
+        ws = tickets = None
+        if nsplit > 1:
+            ws = workspace.get("attn_anc", ws_floats, torch.float32, q.device)
+            tickets = workspace.get_zeroed("attn_anc_tickets", n_tickets, torch.int32, q.device)
+        e.attn_decode_anc(q, k_cache, v_cache, beam_anc, int(num_beams), slot_t, kv_start, key_mask, out, t_cap, ws,
+                          tickets)
+        return out
     if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
         _check_kv8_pair(k_cache, v_cache)
         if out_packed is not None:
@@ -1157,6 +1190,17 @@ def kv_beam_reorder(cache, beam_idx: torch.Tensor, k: int) -> None:
             ref.kv_beam_reorder(t, beam_idx, k, int(cache.index_t.item()))
         else:
             ext().kv_beam_reorder(t, beam_idx.reshape(-1), cache.index_t, int(k))
+
+
+def beam_anc_update(anc: torch.Tensor, beam_idx: torch.Tensor, k: int, slot: torch.Tensor) -> None:
+    """The indirect beam cache's step, in place on the ancestry table uint8 ``[B*k, T]``: every row takes its parent's
+    columns below the slot counter, ``anc[b*k + j, t] <- anc[b*k + beam_idx[b, j], t]`` for ``t < slot[0]``
+    (``ref.beam_anc_update``; csrc/kernels/beam.hip). One launch; groups whose ``beam_idx`` is the identity are
+    skipped; columns at or past the counter keep their content."""
+    if not _is_gpu(anc):
+        ref.beam_anc_update(anc, beam_idx, k, int(slot.item()))
+    else:
+        ext().beam_anc_update(anc, beam_idx.reshape(-1), slot, int(k))
 
 
 # ---------------------------------------------------------------------------------- logits processors

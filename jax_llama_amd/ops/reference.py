@@ -768,6 +768,44 @@ def kv_beam_reorder(t: torch.Tensor, beam_idx: torch.Tensor, k: int, count: int)
     return t
 
 
+# ---- the indirect beam cache: nothing moves, every beam carries an ancestry table (README, "Beam search")
+def beam_anc_init(batch: int, k: int, max_length: int, prompt_len: int, device="cpu") -> torch.Tensor:
+    """uint8 ``[batch * k, max_length]``: 0 in the prompt columns ``[0, prompt_len)`` (every beam reads the prompt from
+    beam 0's row), the identity ``anc[b*k + j, t] = j`` from there on (a row's new key lands in its own row)."""
+    anc = torch.arange(k, dtype=torch.uint8, device=device).repeat(batch)[:, None].repeat(1, max_length)
+    anc[:, :prompt_len] = 0
+    return anc.contiguous()
+
+
+def beam_anc_update(anc: torch.Tensor, beam_idx: torch.Tensor, k: int, count: int) -> torch.Tensor:
+    """In place on the table uint8 ``[B*K, T]``: ``anc[b*K + j, t] = anc_old[b*K + beam_idx[b, j], t]`` for
+    ``t < count`` (the slot counter after the step); later columns keep their content. The column the step just wrote
+    held the identity until now, so the permutation alone hands every child its parent's row for the newest key too."""
+    b = anc.shape[0] // k
+    src = (torch.arange(b, device=anc.device)[:, None] * k + beam_idx.reshape(b, k).long().to(anc.device)).reshape(-1)
+    n = max(0, min(int(count), anc.shape[1]))
+    anc[:, :n] = anc.index_select(0, src)[:, :n]
+    return anc
+
+
+def gather_anc(cache: torch.Tensor, anc: torch.Tensor, k: int) -> torch.Tensor:
+    """The cache ``[B*K, Hkv, T, Dh]`` each logical row reads through its table: slot t of row ``r = b*K + j`` is slot
+    t of physical row ``b*K + min(anc[r, t], K - 1)``."""
+    rows, hkv, t, _ = cache.shape
+    base = torch.arange(rows, device=cache.device) // k * k
+    src = base[:, None] + anc.long().to(cache.device).clamp(max=k - 1)  # [rows, T]
+    return cache[src[:, None, :], torch.arange(hkv, device=cache.device)[None, :, None],
+                 torch.arange(t, device=cache.device)[None, None, :]]
+
+
+def attention_anc(q, k_cache, v_cache, slot0: int, kv_start: torch.Tensor, anc: torch.Tensor, num_beams: int,
+                  key_mask: Optional[torch.Tensor] = None):
+    """``attention`` with every key slot read through the ancestry table: the rows are gathered, the rest is
+    ``attention`` unchanged."""
+    return attention(q, gather_anc(k_cache, anc, num_beams), gather_anc(v_cache, anc, num_beams), slot0, kv_start,
+                     key_mask)
+
+
 # ----------------------------------------------------------------------------------
 # Logits processors (the README's "Logits processors" section is the definition)
 # ----------------------------------------------------------------------------------

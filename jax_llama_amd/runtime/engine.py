@@ -534,14 +534,25 @@ class BeamEngine(DecodeEngine):
     ``topk_candidates(2K)``, the rows' log-sum-exp, ``beam_alive`` + ``beam_step`` (the selection and the whole state
     update, on the device) and ``kv_beam_reorder`` (every beam's cache rows follow its parent): fixed-shape, captured
     once and replayed. Once the loop condition fails (``alive == 0``) a replayed step changes nothing, so the host
-    polls ``alive`` only every ``check_every`` steps."""
+    polls ``alive`` only every ``check_every`` steps.
+
+    ``beam_cache`` (default: the model's, ``set_beam_cache``): ``"indirect"`` moves no cache row. The cache carries an
+    ancestry table (``cache.beam_anc`` uint8 ``[B*K, T]``, ``cache.beam_k``) that decode attention reads K / V
+    through, the prompt cache lands in beam 0's row of each prompt only, and the step's ``reorder`` hook is the
+    table's permutation (``ops.beam_anc_update``) instead of ``kv_beam_reorder``. bf16 KV cache only."""
 
     def __init__(self, model, batch_size: int, num_beams: int, max_length: int, use_graph: Optional[bool] = None,
-                 check_every: int = 16):
+                 check_every: int = 16, beam_cache: Optional[str] = None):
         if model.comm.size > 1:
             raise NotImplementedError("beam search under tensor parallelism (vocab-parallel logits) is not supported")
         if not 2 <= num_beams <= ops.BEAM_MAX:
             raise ValueError(f"num_beams must be in [2, {ops.BEAM_MAX}], got {num_beams}")
+        self.beam_cache = getattr(model, "beam_cache", "reorder") if beam_cache is None else beam_cache
+        if self.beam_cache not in ("reorder", "indirect"):
+            raise ValueError(f"beam_cache must be 'reorder' or 'indirect', got {self.beam_cache!r}")
+        if self.beam_cache == "indirect" and getattr(model, "kv_cache_format", "bf16") != "bf16":
+            raise ValueError("the indirect beam cache reads a bf16 KV cache only (set_kv_cache_format('bf16') or "
+                             "set_beam_cache('reorder'))")
         super().__init__(model, batch_size * num_beams, max_length, use_graph, check_every)
         self.nb, self.k = batch_size, num_beams
         dev = self.device
@@ -555,6 +566,10 @@ class BeamEngine(DecodeEngine):
         self.inv_pen = torch.ones(max_length + 1, dtype=torch.float32, device=dev)
         self.prompt_len = 0
         self.reorder = ops.kv_beam_reorder  # (cache, beam_idx, K), in place
+        if self.beam_cache == "indirect":
+            self.cache.beam_anc = ref.beam_anc_init(batch_size, num_beams, max_length, 0, dev)
+            self.cache.beam_k = num_beams
+            self.reorder = _anc_reorder
         self.beam_idx_log: Optional[list] = None  # eager runs: a list here receives every step's beam_idx (CPU copy)
 
     def _beam_select(self, logits: torch.Tensor):
@@ -602,10 +617,16 @@ class BeamEngine(DecodeEngine):
                                           logits_mode="last")
             parts.append(lg)
         logits = parts[0] if len(parts) == 1 else torch.cat(parts)
-        # ... broadcast to the K beams of each prompt
+        # ... broadcast to the K beams of each prompt; the indirect cache: into beam 0's row only, where the fresh
+        # table (0 in the prompt columns, the identity from S on) sends every beam
         self.cache.reset()
         for dst, src in zip(ops.kv_beam_tensors(self.cache), ops.kv_beam_tensors(tmp)):
-            dst.unflatten(1, (b, k))[:, :, :, :, :s].copy_(src.unsqueeze(2))
+            if self.beam_cache == "indirect":
+                dst.unflatten(1, (b, k))[:, :, 0, :, :s].copy_(src)
+            else:
+                dst.unflatten(1, (b, k))[:, :, :, :, :s].copy_(src.unsqueeze(2))
+        if self.beam_cache == "indirect":
+            self.cache.beam_anc.copy_(ref.beam_anc_init(b, k, self.max_length, s, dev))
         del tmp
         self.cache.advance(s)
         ext_mask = torch.ones(b, self.max_length, dtype=torch.int32)
@@ -642,7 +663,7 @@ class BeamEngine(DecodeEngine):
         # "never" (beam_alive); pad and length_penalty are listed although the step reads them from device buffers
         gc = self.gc
         return (self.k, self.prompt_len, float(gc.length_penalty), gc.early_stopping, int(gc.pad_token_id),
-                int(gc.eos_token_id), self.cache.kv_format, self.key_mask is not None, ops.workspace.generation,
+                int(gc.eos_token_id), self.cache.kv_format, self.beam_cache, self.key_mask is not None, ops.workspace.generation,
                 ops.QKV_ATTN, self.model.comm.reduce_dtype)
 
     def _poll(self) -> bool:
@@ -657,6 +678,11 @@ class BeamEngine(DecodeEngine):
         scores = torch.where(any_fin[:, None], self.score, self.running_score)
         n = self.gc.num_return_sequences
         return seqs[:, :n].reshape(-1, self.max_length).clone(), scores[:, :n].reshape(-1).clone()
+
+
+def _anc_reorder(cache, beam_idx, k):
+    """The indirect beam cache's ``reorder`` hook: the rows stay, the ancestry table takes the permutation."""
+    ops.beam_anc_update(cache.beam_anc, beam_idx, k, cache.index_t)
 
 
 _ENGINES: "OrderedDict" = OrderedDict()
@@ -686,7 +712,7 @@ def get_engine(model, batch_size: int, max_length: int, num_beams: int = 1) -> D
     LRU order and bounded by the bytes of their KV caches. The model's KV-cache format is part of the key: an engine
     owns a cache of one format. ``num_beams > 1``: a BeamEngine over ``B * num_beams`` cache rows."""
     fmt = getattr(model, "kv_cache_format", "bf16")
-    key = (id(model), batch_size, max_length, fmt, num_beams)
+    key = (id(model), batch_size, max_length, fmt, num_beams, getattr(model, "beam_cache", "reorder"))
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)

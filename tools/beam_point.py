@@ -2,12 +2,15 @@
 """Beam-search decode points on a synthetic model, one JSON line each:
 
   * ``beam_decode``: ms per hipGraph-replayed step of a beam search (``--batch`` prompts x ``--beams``) against greedy
-    decoding of the same number of cache rows (``batch * beams``), in one process, alternating, prefill excluded;
+    decoding of the same number of cache rows (``batch * beams``), in one process, alternating, prefill excluded, for
+    every ``--beam-cache`` mode (``reorder``: the cache rows follow the beams; ``indirect``: an ancestry table does,
+    bf16 cache only), with the kernel nodes of the captured step;
   * ``kv_beam_reorder``: the cache reorder alone at the model's cache shape with ``--slots`` valid slots, for an
     all-identity ``beam_idx`` (every group skipped) and a rotation (every row moves): time per call (all launches of
     one step: 2 for a bf16 cache, 4 for FP8) and GB/s over the bytes read plus written, counted from the shapes.
 
   python tools/beam_point.py --model llama3-8b --batch 4 --beams 4 --steps 64 --slots 160 8192
+  python tools/beam_point.py --beam-cache reorder indirect --prompt-len 8192 --gen-len 128 --slots
 """
 from __future__ import annotations
 
@@ -19,12 +22,14 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
-def beam_latency(model, batch, beams, prompt_len, gen_len, steps):
+def beam_latency(model, batch, beams, prompt_len, gen_len, steps, beam_cache="reorder"):
+    """(ms per replayed step, kernel nodes of the captured step)"""
     import torch
-    from jax_llama_amd.runtime.benchmark import synthetic_prompts
+    from jax_llama_amd.runtime.benchmark import graph_kernels, synthetic_prompts
     from jax_llama_amd.runtime.engine import BeamEngine, GenerationConfig
     max_len = prompt_len + gen_len
-    eng = BeamEngine(model, batch, beams, max_len, use_graph=True)
+    eng = BeamEngine(model, batch, beams, max_len, use_graph=True, beam_cache=beam_cache)
+    eng.keep_graph = True
     eng.gc = GenerationConfig(max_length=max_len, num_beams=beams, pad_token_id=0, eos_token_id=-1)
     prompts = synthetic_prompts(model.config.vocab_size, batch, prompt_len, 0)
     eng.prefill(prompts, None)
@@ -40,7 +45,7 @@ def beam_latency(model, batch, beams, prompt_len, gen_len, steps):
     ev1.record()
     torch.cuda.synchronize()
     assert int(eng.alive.item()) == 1 and int(eng.cur_len.item()) == prompt_len + 1 + steps
-    return ev0.elapsed_time(ev1) / steps
+    return ev0.elapsed_time(ev1) / steps, graph_kernels(eng._graph)
 
 
 def reorder_points(cfg, n_kv_heads, head_dim, rows, beams, slots, kv):
@@ -90,6 +95,7 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--slots", type=int, nargs="*", default=[160, 8192])
     ap.add_argument("--kv", nargs="+", choices=["bf16", "fp8"], default=["bf16"])
+    ap.add_argument("--beam-cache", nargs="+", choices=["reorder", "indirect"], default=["reorder"])
     args = ap.parse_args()
     import torch
     from jax_llama_amd.config import get_preset
@@ -97,20 +103,23 @@ def main():
     from jax_llama_amd.runtime.benchmark import decode_latency
     if not torch.cuda.is_available():
         raise SystemExit("beam_point.py measures on the GPU: none found")
-    cfg = get_preset(args.model, max_seq_len=2048)
+    cfg = get_preset(args.model, max_seq_len=max(2048, args.prompt_len + args.gen_len))
     model = LLaMAForCausalLM(cfg, device="cuda", _do_init=False).init_random(seed=1)
     rows = args.batch * args.beams
     for kv in args.kv:
         model.set_kv_cache_format("fp8_e4m3" if kv == "fp8" else "bf16")
         for rep in range(args.reps):
             g = decode_latency(model, rows, args.prompt_len, args.gen_len, steps=args.steps)
-            b = beam_latency(model, args.batch, args.beams, args.prompt_len, args.gen_len, args.steps)
-            print(json.dumps({"what": "beam_decode", "model": args.model, "kv": kv, "rep": rep, "batch": args.batch,
-                              "beams": args.beams, "prompt_len": args.prompt_len, "steps": args.steps,
-                              "beam_ms_per_step": round(b, 4), "greedy_rows": rows,
-                              "greedy_ms_per_step": g["decode_ms_per_token"],
-                              "beam_over_greedy": round(b / g["decode_ms_per_token"], 4)}), flush=True)
-            torch.cuda.empty_cache()
+            for mode in args.beam_cache:
+                if mode == "indirect" and kv != "bf16":
+                    continue  # (the ancestry kernel reads a bf16 cache only)
+                b, nodes = beam_latency(model, args.batch, args.beams, args.prompt_len, args.gen_len, args.steps, mode)
+                print(json.dumps({"what": "beam_decode", "model": args.model, "kv": kv, "beam_cache": mode, "rep": rep,
+                                  "batch": args.batch, "beams": args.beams, "prompt_len": args.prompt_len,
+                                  "steps": args.steps, "beam_ms_per_step": round(b, 4), "kernel_nodes": nodes,
+                                  "greedy_rows": rows, "greedy_ms_per_step": g["decode_ms_per_token"],
+                                  "beam_over_greedy": round(b / g["decode_ms_per_token"], 4)}), flush=True)
+                torch.cuda.empty_cache()
     heads, hd = model.n_kv_heads, model.head_dim
     for kv in args.kv:
         if args.slots:
