@@ -69,18 +69,19 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
          top_p: float = 0.95, weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1,
          repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0, min_new_tokens: int = 0,
          quantized_gemm: str = "dequant", top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0,
-         beam_cache: str = "reorder"):
+         beam_cache: str = "reorder", prompt_lookup: int = 0):
     """Reference ``main`` (jax_example.py:33-40). ``num_beams > 1``: beam search (temperature is then taken as 0).
     Llama-3 (without beam search) stops on any of the tokenizer's ``stop_tokens`` (end of text, end of turn)."""
     generator = load(ckpt_dir, tokenizer_path, is_llama3, weights=weights, kv_cache=kv_cache,
                      quantized_gemm=quantized_gemm, beam_cache=beam_cache)
-    if num_beams > 1:
+    if num_beams > 1 or prompt_lookup > 0:  # neither samples
         temperature = 0.0
     stops = sorted(generator.tokenizer.stop_tokens) if is_llama3 and num_beams == 1 else None
     results = generator.generate_from_str(PROMPTS, max_gen_len=max_gen_len, temperature=temperature, top_p=top_p,
                                           num_beams=num_beams, repetition_penalty=repetition_penalty,
                                           no_repeat_ngram_size=no_repeat_ngram_size, min_new_tokens=min_new_tokens,
-                                          stop_token_ids=stops, top_k=top_k, min_p=min_p, typical_p=typical_p)
+                                          stop_token_ids=stops, top_k=top_k, min_p=min_p, typical_p=typical_p,
+                                          prompt_lookup_num_tokens=prompt_lookup or None)
     if int(os.environ.get("RANK", "0")) == 0:
         for result in results:
             print(result)
@@ -91,7 +92,8 @@ def main(ckpt_dir: str, tokenizer_path: str, is_llama3: bool, max_gen_len: int =
 def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, temperature: float, top_p: float,
               weights: str = "bf16", kv_cache: str = "bf16", num_beams: int = 1, repetition_penalty: float = 1.0,
               no_repeat_ngram_size: int = 0, min_new_tokens: int = 0, quantized_gemm: str = "dequant",
-              top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0, beam_cache: str = "reorder"):
+              top_k: int = 50, min_p: float = 0.0, typical_p: float = 1.0, beam_cache: str = "reorder",
+              prompt_lookup: int = 0):
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.runtime.engine import GenerationConfig
     ctx = init_distributed()
@@ -107,7 +109,10 @@ def synthetic(model_name: str, batch: int, prompt_len: int, max_gen_len: int, te
     model.set_beam_cache(beam_cache)
     toks = torch.randint(3, cfg.vocab_size, (batch, prompt_len), generator=torch.Generator().manual_seed(0),
                          dtype=torch.int32)
+    if prompt_lookup > 0:
+        temperature = 0.0
     gc = GenerationConfig(max_length=prompt_len + max_gen_len, do_sample=temperature != 0.0 and num_beams == 1,
+                          prompt_lookup_num_tokens=prompt_lookup or None,
                           temperature=temperature, top_p=top_p, top_k=top_k, pad_token_id=0, eos_token_id=-1,
                           num_beams=num_beams, min_p=min_p, typical_p=typical_p,
                           repetition_penalty=repetition_penalty, no_repeat_ngram_size=no_repeat_ngram_size,
@@ -160,14 +165,17 @@ if __name__ == "__main__":
                     help="logits processor: no n-gram of this size occurs twice in a row's history (0: off)")
     ap.add_argument("--min_new_tokens", type=int, default=0,
                     help="logits processor: the stop tokens are banned for this many generated tokens")
+    ap.add_argument("--prompt-lookup", type=int, default=0, metavar="K",
+                    help="K > 0: greedy decoding with prompt-lookup speculation, K draft tokens per step from the row's "
+                    "own history (GenerationConfig.prompt_lookup_num_tokens; no sampling, no beams, no tensor parallelism)")
     a = ap.parse_args()
     if a.synthetic:
         synthetic(a.model, a.batch, a.prompt_len, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
                   a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k,
-                  a.min_p, a.typical_p, a.beam_cache)
+                  a.min_p, a.typical_p, a.beam_cache, a.prompt_lookup)
     else:
         if not (a.ckpt_dir and a.tokenizer_path):
             ap.error("--ckpt_dir and --tokenizer_path are required (or use --synthetic)")
         main(a.ckpt_dir, a.tokenizer_path, a.is_llama3, a.max_gen_len, a.temperature, a.top_p, a.weights, a.kv_cache,
              a.num_beams, a.repetition_penalty, a.no_repeat_ngram_size, a.min_new_tokens, a.quantized_gemm, a.top_k,
-             a.min_p, a.typical_p, a.beam_cache)
+             a.min_p, a.typical_p, a.beam_cache, a.prompt_lookup)

@@ -1171,6 +1171,82 @@ void attn_decode_anc(Tensor q, Tensor k_cache, Tensor v_cache, Tensor anc, int64
      "attn_decode_anc");
 }
 
+// decode attention for a few queries per row (kernels/attn_verify.hip): q bf16 [B, S, H, 128], bf16 caches
+void attn_verify(Tensor q, Tensor k_cache, Tensor v_cache, Tensor slot, Tensor kv_start, Tensor out, int64_t t_cap,
+                 c10::optional<Tensor> ws, c10::optional<Tensor> tickets) {
+  for (auto* t : {&q, &k_cache, &v_cache, &slot, &kv_start, &out}) check_gpu(*t, "attn_verify arg");
+  check(q.scalar_type() == torch::kBFloat16 && out.scalar_type() == torch::kBFloat16 && q.dim() == 4,
+        "attn_verify: q bf16 [B, S, H, Dh]");
+  const int64_t b = q.size(0), s = q.size(1), h = q.size(2), dh = q.size(3);
+  check(k_cache.scalar_type() == torch::kBFloat16 && v_cache.scalar_type() == torch::kBFloat16 && k_cache.dim() == 4 &&
+            k_cache.sizes() == v_cache.sizes() && k_cache.size(0) == b && k_cache.size(3) == dh,
+        "attn_verify: caches bf16 [B, Hkv, T, Dh]");
+  const int64_t hkv = k_cache.size(1), T = k_cache.size(2);
+  check(T >= 1 && T < (1 << 30), "attn_verify: 1 <= T < 2^30");
+  check(slot.scalar_type() == torch::kInt32 && slot.numel() >= 1 && kv_start.scalar_type() == torch::kInt32 &&
+            kv_start.numel() == b,
+        "slot/kv_start");
+  check(out.numel() == q.numel(), "attention out shape");
+  check(t_cap >= 0 && t_cap <= T, "t_cap exceeds the cache length");
+  check(b <= 65535 && hkv <= 65535, "attn_verify: at most 65535 rows and kv heads");
+  const jla::AttnVerifyPlanResult r = jla::attn_verify_plan(jla::attn_knobs(), b, s, h, hkv, dh, t_cap, false, false, false);
+  TORCH_CHECK(r.rc == 0, "jax_llama_amd._C: attn_verify: no plan (", r.why, "; see attn_plan.h)");
+  float* wsp = nullptr;
+  int32_t* tkp = nullptr;
+  if (r.plan.nsplit > 1) {
+    TORCH_CHECK(ws.has_value() && tickets.has_value(), "jax_llama_amd._C: attn_verify: the plan splits the keys (nsplit ",
+                r.plan.nsplit, "): ws and tickets are required (attn_verify_plan_check)");
+    check_gpu(*ws, "ws");
+    check_gpu(*tickets, "tickets");
+    TORCH_CHECK(ws->scalar_type() == torch::kFloat32 && ws->device() == q.device() &&
+                    (size_t)ws->numel() >= r.plan.ws_floats,
+                "jax_llama_amd._C: attn_verify: ws must be fp32 on q's device with at least ", r.plan.ws_floats,
+                " floats (attn_verify_plan_check)");
+    TORCH_CHECK(tickets->scalar_type() == torch::kInt32 && tickets->device() == q.device() &&
+                    tickets->numel() >= r.plan.tickets,
+                "jax_llama_amd._C: attn_verify: tickets must be int32 on q's device, one per (row, kv head) pair = ",
+                r.plan.tickets, " (attn_verify_plan_check)");
+    wsp = ptr<float>(*ws);
+    tkp = ptr<int32_t>(*tickets);
+  }
+  rc(jla::attn_verify(cbf(q), cbf(k_cache), cbf(v_cache), ptr<int32_t>(slot), ptr<int32_t>(kv_start), bf(out), b, s, h,
+                      hkv, dh, T, t_cap, stream(), wsp, r.plan.ws_floats, tkp, r.plan.tickets),
+     "attn_verify");
+}
+
+// ---- the prompt-lookup speculative loop (kernels/spec.hip) ----
+void prompt_lookup(Tensor sequences, Tensor cur_len, Tensor hist_start, Tensor tokens, int64_t max_ngram) {
+  for (auto* t : {&sequences, &cur_len, &hist_start, &tokens}) {
+    check_gpu(*t, "prompt_lookup arg");
+    check(t->scalar_type() == torch::kInt32, "prompt_lookup: int32 tensors");
+  }
+  check(sequences.dim() == 2 && tokens.dim() == 2 && tokens.size(0) == sequences.size(0) && tokens.size(1) >= 2 &&
+            tokens.size(1) <= 64 && hist_start.numel() == sequences.size(0) && cur_len.numel() == 1,
+        "prompt_lookup shapes: sequences [B, L], tokens [B, k + 1] with 1 <= k <= 63, hist_start [B], cur_len [1]");
+  check(max_ngram >= 1 && max_ngram <= sequences.size(1), "prompt_lookup: 1 <= max_ngram <= L");
+  rc(jla::prompt_lookup(ptr<int32_t>(sequences), ptr<int32_t>(cur_len), ptr<int32_t>(hist_start), ptr<int32_t>(tokens),
+                        sequences.size(0), sequences.size(1), tokens.size(1) - 1, max_ngram, stream()),
+     "prompt_lookup");
+}
+
+void spec_accept(Tensor tgt, Tensor finished, Tensor sequences, Tensor cur_len, Tensor tokens, Tensor positions,
+                 Tensor slot, int64_t pad, Tensor stop) {
+  for (auto* t : {&tgt, &finished, &sequences, &cur_len, &tokens, &positions, &slot, &stop}) {
+    check_gpu(*t, "spec_accept arg");
+    check(t->scalar_type() == torch::kInt32, "spec_accept: int32 tensors");
+  }
+  check(tokens.dim() == 2 && tokens.size(1) >= 2, "spec_accept: tokens [B, k + 1]");
+  const int64_t b = tokens.size(0), s = tokens.size(1);
+  check(b >= 1 && b <= 64, "spec_accept: 1 <= B <= 64 rows");
+  check(tgt.numel() == b * s && positions.numel() == b * s && finished.numel() == b && sequences.dim() == 2 &&
+            sequences.size(0) == b && cur_len.numel() == 1 && slot.numel() == 1 && stop.numel() == 8,
+        "spec_accept shapes (tgt, positions [B, k + 1]; stop: int32 [8])");
+  rc(jla::spec_accept(ptr<int32_t>(tgt), ptr<int32_t>(finished), ptr<int32_t>(sequences), ptr<int32_t>(cur_len),
+                      ptr<int32_t>(tokens), ptr<int32_t>(positions), ptr<int32_t>(slot), b, sequences.size(1), s - 1,
+                      pad, ptr<int32_t>(stop), stream()),
+     "spec_accept");
+}
+
 // ---- custom all-reduce (allreduce.hip) -------------------------------------------------------
 py::tuple car_alloc(int64_t max_bytes, int64_t world) {
   void* buf = nullptr;
@@ -1492,7 +1568,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
     const int r = reset ? 1 : 0;
     return (int64_t)(jla::jla_bounds_norm_embed(r) | jla::jla_bounds_rope_kv(r) | jla::jla_bounds_sample(r) |
                      jla::jla_bounds_gemm(r) | jla::jla_bounds_gemv(r) | jla::jla_bounds_kv8(r) |
-                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_decode_anc(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r) |
+                     jla::jla_bounds_attn_decode(r) | jla::jla_bounds_attn_decode_anc(r) | jla::jla_bounds_attn_verify(r) | jla::jla_bounds_spec(r) | jla::jla_bounds_attn_prefill(r) | jla::jla_bounds_beam(r) |
                      jla::jla_bounds_logits_proc(r));
   }, "OR of the bounds-checked debug build's error words (JLA_BOUNDS_* bits); always 0 in a release build",
         py::arg("reset") = false);
@@ -1644,4 +1720,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {  // _C, or _C_dbg for the bounds-chec
   }, py::arg("b"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"), py::arg("masked"), py::arg("num_beams"));
   m.def("attn_set_anc_splits", [](int64_t n) { jla::attn_set_anc_splits((int)n); },
         "key splits per pair of the beam-ancestry decode attention: 0 by shape, 1 never, n > 1 pinned (tests, A/B)");
+  // decode attention for a few queries per row (kernels/attn_verify.hip)
+  m.def("attn_verify", &attn_verify, py::arg("q"), py::arg("k_cache"), py::arg("v_cache"), py::arg("slot"),
+        py::arg("kv_start"), py::arg("out"), py::arg("t_cap"), py::arg("ws") = py::none(),
+        py::arg("tickets") = py::none());
+  // (rc, why, column tiles, nsplit, ws_floats, tickets) of that launch under the current knobs (kernels/attn_plan.h);
+  // rc != 0: the shape is declined (ops.attention runs attn_prefill)
+  m.def("attn_verify_plan_check", [](int64_t b, int64_t s, int64_t h, int64_t hkv, int64_t dh, int64_t t_cap,
+                                     bool fp8_cache, bool masked, bool anc) {
+    const jla::AttnVerifyPlanResult r = jla::attn_verify_plan(jla::attn_knobs(), (int)b, (int)s, (int)h, (int)hkv,
+                                                              (int)dh, (int)t_cap, fp8_cache, masked, anc);
+    return py::make_tuple(r.rc, r.why, r.plan.tiles, r.plan.nsplit, (int64_t)r.plan.ws_floats, r.plan.tickets);
+  }, py::arg("b"), py::arg("s"), py::arg("h"), py::arg("hkv"), py::arg("dh"), py::arg("t_cap"),
+        py::arg("fp8_cache") = false, py::arg("masked") = false, py::arg("anc") = false);
+  m.def("attn_set_verify_splits", [](int64_t n) { jla::attn_set_verify_splits((int)n); },
+        "key splits per pair of the few-query decode attention: 0 by shape, 1 never, n > 1 pinned (tests, A/B)");
+  // the prompt-lookup speculative loop (kernels/spec.hip)
+  m.def("prompt_lookup", &prompt_lookup, py::arg("sequences"), py::arg("cur_len"), py::arg("hist_start"),
+        py::arg("tokens"), py::arg("max_ngram"));
+  m.def("spec_accept", &spec_accept, py::arg("tgt"), py::arg("finished"), py::arg("sequences"), py::arg("cur_len"),
+        py::arg("tokens"), py::arg("positions"), py::arg("slot"), py::arg("pad"), py::arg("stop"));
 }

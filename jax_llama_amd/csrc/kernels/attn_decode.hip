@@ -739,6 +739,7 @@ void attn_set_v6_wpp(int wpp) { g_attn_knobs.v6_wpp = (wpp == 1 || wpp == 2 || w
 void attn_set_q8_waves(int waves) { g_attn_knobs.q8_waves = (waves == 1 || waves == 2 || waves == 4 || waves == 8) ? waves : 0; }
 void attn_set_q8_splits(int n) { g_attn_knobs.q8_splits = n > 0 ? n : 0; }
 void attn_set_anc_splits(int n) { g_attn_knobs.anc_splits = n > 0 ? n : 0; }
+void attn_set_verify_splits(int n) { g_attn_knobs.verify_splits = n > 0 ? n : 0; }
 void attn_set_q8_prefill(int mode) { g_attn_knobs.q8_prefill = (mode == 0 || mode == 1) ? mode : -1; }
 
 // Launches the kernel attn_decode_plan() names: each JLA_AD* row below maps plan fields to one instantiation (a plan

@@ -32,6 +32,7 @@ struct AttnKnobs {
   int q8_waves = 0;         // the fp8 KV cache's kernel (attn_decode_q8_plan): waves per pair pinned to 1 / 8 (VALU forms) or 2 / 4 (the matrix-core form); 0 = by shape
   int q8_splits = 0;        // ... its key splits per pair: 0 = by shape, 1 = never, n > 1 pinned (clamped to the chunks of t_cap)
   int anc_splits = 0;       // the beam-ancestry kernel (attn_decode_anc_plan): key splits per pair, 0 = by shape, 1 = never, n > 1 pinned
+  int verify_splits = 0;    // the few-query kernel (attn_verify_plan): key splits per pair, 0 = by shape, 1 = never, n > 1 pinned
   int q8_prefill = -1;      // S > 1 on the fp8 KV cache (attn_prefill_q8_plan): -1 = by shape, 0 = always dequantise, 1 = always direct
 };
 
@@ -348,6 +349,79 @@ inline AttnAncPlanResult attn_decode_anc_plan(const AttnKnobs& k, int B, int H, 
   }
   if (p.nsplit > 1) {
     p.ws_floats = (size_t)B * H * p.nsplit * ATTN_PART_FLOATS;
+    p.tickets = pairs;
+  }
+  return {0, "", p};
+}
+
+// ---- a few queries per row (attn_verify.hip: the verify step of speculative decoding, 2 <= S, S x rep <= 32): the
+// columns of one or two 16-column MFMA tiles are (query position, head of the pair), one 4-wave workgroup per (row, kv
+// head, key split), the splits merged by a last arriver. ops.attention(few_query=True) asks this plan; a shape it
+// refuses runs attn_prefill as before.
+constexpr int ATTN_VERIFY_WAVES = 4;            // waves per workgroup, interleaving the split's 32-key steps
+constexpr int ATTN_VERIFY_MAX_COLS = 32;        // S x rep: two column tiles
+constexpr int ATTN_VERIFY_SPLIT_WGS = 256;      // key splits until pairs x splits reaches this many workgroups ...
+constexpr int ATTN_VERIFY_SPLIT_MIN_STEPS = 16;  // ... of at least this many 32-key steps of t_cap each (4 per wave)
+constexpr int ATTN_VERIFY_MAX_SPLITS = 64;      // what a pinned count is cut to (the merge is one workgroup's)
+struct AttnVerifyPlan {
+  int rep;     // query heads per kv head
+  int tiles;   // 16-column MFMA tiles: 1 (S x rep <= 16) or 2
+  int nsplit;  // key splits per pair (1: no workspace)
+  size_t ws_floats;  // nsplit > 1: the launch is given this many floats, [m, l, 0, 0, o[128]] per column and split ...
+  int tickets;       // ... and this many zero-initialised int32 tickets, one per pair (self-resetting); 0 / 0 unsplit
+};
+struct AttnVerifyPlanResult {
+  int rc;           // 0 served; -1 declined (the caller runs attn_prefill)
+  const char* why;  // the rule that declined the call
+  AttnVerifyPlan plan;
+};
+inline AttnVerifyPlanResult attn_verify_plan(const AttnKnobs& k, int B, int S, int H, int Hkv, int Dh, int t_cap,
+                                             bool fp8_cache, bool masked, bool anc) {
+  const auto fail = [](const char* why) { return AttnVerifyPlanResult{-1, why, AttnVerifyPlan{}}; };
+  if (fp8_cache) return fail("few queries: bf16 caches only");
+  if (masked) return fail("few queries: no key mask");
+  if (anc) return fail("few queries: no beam ancestry table");
+  if (Dh != ATTN_DH) return fail("head dim: Dh == 128");
+  if (H < 1 || Hkv < 1 || H % Hkv) return fail("GQA: H a positive multiple of Hkv");
+  const int rep = H / Hkv, pairs = B * Hkv;
+  if (rep > 8 || (rep & (rep - 1))) return fail("few queries: query heads per kv head 1, 2, 4 or 8");
+  if (S < 2 || S * rep > ATTN_VERIFY_MAX_COLS) return fail("few queries: 2 <= S and S x rep <= 32");
+  AttnVerifyPlan p{};
+  p.rep = rep, p.tiles = S * rep <= 16 ? 1 : 2, p.nsplit = 1;
+  // ---- key splits: enough workgroups to cover the CUs when pairs are few and t_cap is long, each split keeping whole
+  // 32-key steps and at least 16 of them (4 per wave) so that its stream outlasts the merge it causes. Records
+  // (profiles/attn_verify_ab.jsonl; Llama-3-8B heads, graph-timed, cold K / V, medians of 9 rounds, us; "u" unsplit,
+  // then pinned counts; attn_prefill on the same launch in brackets), the last query at the end of the context:
+  //   B = 1  S = 4  ctx 512:   u 11.9   2: 11.8   8: 13.7   16: 17.7   (22.9)
+  //                 ctx 4096:  u 52.2   8: 18.2   16: 20.8   64: 46.4  (152.4)
+  //                 ctx 32768: u 364.6  8: 71.5   32: 65.2   64: 81.3  (1155)
+  //          S = 8  ctx 512:   u 16.3   2: 17.9   8: 20.7              (22.9)
+  //                 ctx 4096:  u 55.1   8: 24.8   16: 29.6   64: 86.8  (151.7)
+  //                 ctx 32768: u 360.5  8: 76.3   32: 79.8   64: 121.0 (1151)
+  //   B = 8  S = 4  ctx 512:   u 14.0   2: 13.9   8: 18.1              (24.5)
+  //                 ctx 4096:  u 66.0   4: 54.3   8: 56.8   64: 170.7  (165.0)
+  //                 ctx 32768: u 411.2  4: 237.6  8: 237.1  64: 359.4  (1168)
+  //          S = 8  ctx 512:   u 16.4   2: 18.4   8: 41.5              (24.1)
+  //                 ctx 4096:  u 67.8   4: 59.0   8: 74.1   64: 539.7  (166.1)
+  //                 ctx 32768: u 407.8  4: 241.9  8: 245.7  64: 715.1  (1172)
+  // So: 8-step splits (the first guess: 2 at ctx 512, 16 at 4096) tie or lose to 16-step ones (1 and 8) everywhere they
+  // differ, hence 16; one workgroup per CU stays the count to aim for (B = 8: 4 splits = 256 workgroups is best or
+  // tied), and many short splits lose badly to their merge (64 at B = 8). At B = 1, ctx 32768 the rule's 32 splits and
+  // 8 are within 10 % of each other either way; not refined further.
+  // A pinned count (verify_splits > 1) is cut so that no split is emptier than one step at t_cap.
+  if (B > 0 && k.verify_splits != 1) {
+    int ns, most;
+    if (k.verify_splits > 1) {
+      ns = k.verify_splits < ATTN_VERIFY_MAX_SPLITS ? k.verify_splits : ATTN_VERIFY_MAX_SPLITS;
+      most = (t_cap + 31) / 32;
+    } else {
+      ns = (ATTN_VERIFY_SPLIT_WGS + pairs - 1) / pairs;
+      most = t_cap / (ATTN_VERIFY_SPLIT_MIN_STEPS * 32);
+    }
+    p.nsplit = ns > most ? (most < 1 ? 1 : most) : ns;
+  }
+  if (p.nsplit > 1) {
+    p.ws_floats = (size_t)pairs * p.nsplit * (16 * p.tiles) * ATTN_PART_FLOATS;
     p.tickets = pairs;
   }
   return {0, "", p};

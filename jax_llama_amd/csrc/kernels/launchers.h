@@ -216,6 +216,25 @@ int attn_decode_anc(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const u
                     const int32_t* slot, const int32_t* kv_start, const uint8_t* key_mask, int mask_len, bf16_t* out,
                     int B, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws = nullptr,
                     size_t ws_floats = 0, int32_t* tickets = nullptr, int n_tickets = 0);
+// ---- a few queries per row (attn_verify.hip): q [B, S, H, 128] at slots slot[0] .. + S - 1, bf16 caches, out
+// [B * S, H * 128] as attn_prefill writes it. Launched as attn_verify_plan() (attn_plan.h) says; returns the plan's rc
+// where it declines. Where the plan splits the keys ws / tickets hold the plan's ws_floats / tickets (tickets
+// zero-initialised once, self-resetting), -2 if they do not; an unsplit launch ignores them.
+void attn_set_verify_splits(int n);  // its key splits per pair: 0 by shape, 1 never, n > 1 pinned (the plan clamps it)
+unsigned jla_bounds_attn_verify(int reset);
+int attn_verify(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
+                bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T, int t_cap, hipStream_t s, float* ws = nullptr,
+                size_t ws_floats = 0, int32_t* tickets = nullptr, int n_tickets = 0);
+// ---- the prompt-lookup speculative loop (spec.hip; ops/reference.py prompt_lookup / spec_accept, exact).
+// prompt_lookup: tokens [B, k + 1], columns 1 .. k <- the k draft tokens of each row from its own history
+// sequences[b, hist_start[b] : cur_len[0]] (n-grams of max_ngram .. 1 tokens). spec_accept: drafts = tokens[:, 1:]
+// against the verify step's greedy tokens tgt [B, k + 1]; appends the accepted run to sequences, advances cur_len,
+// positions [B, k + 1] and the slot counter by it and writes tokens[:, 0]. B <= 64, stop int32[8].
+unsigned jla_bounds_spec(int reset);
+int prompt_lookup(const int32_t* sequences, const int32_t* cur_len, const int32_t* hist_start, int32_t* tokens, int B,
+                  int L, int k, int max_ngram, hipStream_t s);
+int spec_accept(const int32_t* tgt, int32_t* finished, int32_t* sequences, int32_t* cur_len, int32_t* tokens,
+                int32_t* positions, int32_t* slot, int B, int L, int k, int pad, const int32_t* stop, hipStream_t s);
 void attn_prefill_set_impl(int impl);  // 2 = GQA-shared MFMA 32x32 flash kernel (default), 1 = v1
 int attn_prefill(const bf16_t* q, const bf16_t* kc, const bf16_t* vc, const int32_t* slot, const int32_t* kv_start,
                  const uint8_t* key_mask, int mask_len, bf16_t* out, int B, int S, int H, int Hkv, int Dh, int T,

@@ -33,7 +33,7 @@ class LLaMA:
                  top_p: float = 0.95, seed: int = 0, num_beams: int = 1, length_penalty: float = 1.0,
                  early_stopping=False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                  min_new_tokens: int = 0, stop_token_ids=None, top_k: int = 50, min_p: float = 0.0,
-                 typical_p: float = 1.0) -> torch.Tensor:
+                 typical_p: float = 1.0, prompt_lookup_num_tokens=None) -> torch.Tensor:
         """``num_beams > 1``: beam search (``runtime/engine.py`` BeamEngine); it does not sample, so ``temperature``
         must then be 0. Returns each prompt's best hypothesis.
 
@@ -43,7 +43,10 @@ class LLaMA:
 
         ``top_k``: the HF default 50; 0 is no top-k cut (pure nucleus sampling with ``top_p < 1``, pure temperature
         sampling with ``top_p = 1``), see the README's "Full-vocabulary sampling". ``min_p`` (0: off) and ``typical_p``
-        (1: off) are HF's two further truncation rules, applied after top-p (the same section)."""
+        (1: off) are HF's two further truncation rules, applied after top-p (the same section).
+
+        ``prompt_lookup_num_tokens = k``: greedy decoding (``temperature`` 0) with prompt-lookup speculation, up to
+        ``k + 1`` tokens per step (the README's "Prompt-lookup decoding" section)."""
         if num_beams != 1 and temperature != 0.0:
             raise ValueError("beam search does not sample: num_beams > 1 needs temperature=0")
         tokens = torch.as_tensor(tokens, dtype=torch.int32) if not torch.is_tensor(tokens) else tokens
@@ -68,6 +71,7 @@ class LLaMA:
             min_p=min_p,
             typical_p=typical_p,
             seed=seed,
+            prompt_lookup_num_tokens=prompt_lookup_num_tokens,
         )
         out = self.model.generate(tokens, attention_mask=attention_mask, generation_config=gc)
         # the reference's output constraint P("dp", None) keeps the batch split across dp replicas;
@@ -109,7 +113,7 @@ class LLaMA:
                           top_p: float = 0.95, seed: int = 0, num_beams: int = 1, length_penalty: float = 1.0,
                           early_stopping=False, repetition_penalty: float = 1.0, no_repeat_ngram_size: int = 0,
                           min_new_tokens: int = 0, stop_token_ids=None, top_k: int = 50, min_p: float = 0.0,
-                          typical_p: float = 1.0) -> List[str]:
+                          typical_p: float = 1.0, prompt_lookup_num_tokens=None) -> List[str]:
         """``stop_token_ids``: each completion is cut at the first of any of them (default: at ``eos_id``)."""
         tok = self.tokenizer
         prompt_tokens = [tok.encode(x, bos=True, eos=False) for x in prompts]
@@ -120,7 +124,7 @@ class LLaMA:
         attention_mask = (tokens != tok.eos_id).to(torch.int32)
         out_tokens = self.generate(tokens, attention_mask, max_gen_len, temperature, top_p, seed, num_beams,
                                    length_penalty, early_stopping, repetition_penalty, no_repeat_ngram_size,
-                                   min_new_tokens, stop_token_ids, top_k, min_p, typical_p)
+                                   min_new_tokens, stop_token_ids, top_k, min_p, typical_p, prompt_lookup_num_tokens)
         stops = {tok.eos_id} if stop_token_ids is None else {int(t) for t in stop_token_ids}
         # rows of this dp replica only when the outputs could not be gathered (no process group)
         row0 = 0 if out_tokens.shape[0] == len(prompts) else self.mesh.dp_rank * out_tokens.shape[0]

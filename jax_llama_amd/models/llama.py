@@ -483,7 +483,8 @@ class LLaMAForCausalLM:
     def forward_tokens(self, ids: torch.Tensor, positions: torch.Tensor, cache: KVCache, slot0,
                        kv_start: torch.Tensor, key_mask: Optional[torch.Tensor] = None,
                        logits_mode: str = "last", collect_hidden: bool = False,
-                       collect_attn: bool = False, targets: Optional[torch.Tensor] = None):
+                       collect_attn: bool = False, targets: Optional[torch.Tensor] = None,
+                       few_query: bool = False):
         """Run all layers for ``ids [B, S]`` placed at cache slots ``slot0 .. slot0+S-1``.
 
         ``slot0``: int or device int32[1] tensor (graph capture). Returns
@@ -491,15 +492,17 @@ class LLaMAForCausalLM:
         vocab shard: ``[B, V/tp]`` ("last"), ``[B*S, V/tp]`` ("all"), None ("none"), or the
         shard's greedy ``(idx int32[B], val fp32[B])`` of the last position ("argmax"), or the shard's scoring
         triple ``(tgt, mx, se)``, fp32 ``[B*S]`` each, of every position against the global token ids ``targets``
-        int32 ``[B*S]`` ("logprob", ``ops.linear_logprob``: no logits are materialised)."""
+        int32 ``[B*S]`` ("logprob", ``ops.linear_logprob``: no logits are materialised), or the greedy pair of every
+        position, ``[B*S]`` each ("argmax_all": the verify step of prompt-lookup decoding). ``few_query``: the
+        attention launches ask for the few-query decode kernel (``ops.attention``); nothing else changes."""
         if (logits_mode == "logprob") != (targets is not None):
             raise ValueError("logits_mode='logprob' takes `targets` (and no other mode does)")
         with ops.autotune.tp_scope(self.comm):  # TP: rank 0 picks the kernel plans for every rank
             return self._forward_tokens(ids, positions, cache, slot0, kv_start, key_mask, logits_mode,
-                                        collect_hidden, collect_attn, targets)
+                                        collect_hidden, collect_attn, targets, few_query)
 
     def _forward_tokens(self, ids, positions, cache, slot0, kv_start, key_mask, logits_mode, collect_hidden,
-                        collect_attn, targets=None):
+                        collect_attn, targets=None, few_query=False):
         b, s = ids.shape
         d = self.config.hidden_size
         # residual stream: fp32 h plus its bf16 mirror hb (the A operand of every projection
@@ -507,7 +510,8 @@ class LLaMAForCausalLM:
         hb = torch.empty(b * s, d, dtype=BF16, device=self.device)
         h = ops.embedding(ids.reshape(-1), self.wte, mirror=hb)
         hidden, attns = self.blocks(h, hb, positions, cache, slot0, kv_start, key_mask, s,
-                                    output_hidden_states=collect_hidden, output_attentions=collect_attn)
+                                    output_hidden_states=collect_hidden, output_attentions=collect_attn,
+                                    few_query=few_query)
         if logits_mode == "none":
             logits = None
         elif logits_mode == "logprob":  # scoring: this rank's (tgt, mx, se) per position, reduced in the GEMM epilogue
@@ -517,10 +521,12 @@ class LLaMAForCausalLM:
             else:
                 logits = ops.linear_logprob(hb, self.lm_head, targets, rms_eps=self.eps, col_offset=off)
         elif self.precision == "highest":  # fp32 lm_head weights + fp32 GEMM (reference model.py:698-736)
-            hl = h if logits_mode == "all" else h.reshape(b, s, d)[:, -1].contiguous()
+            hl = h if logits_mode in ("all", "argmax_all") else h.reshape(b, s, d)[:, -1].contiguous()
             logits = ops.linear_f32(self.final_norm(hl), self.lm_head_f32)
-            if logits_mode == "argmax":
+            if logits_mode in ("argmax", "argmax_all"):
                 logits = ops.argmax(logits.contiguous())
+        elif logits_mode == "argmax_all":
+            logits = ops.linear_argmax(hb, self.lm_head, rms_eps=self.eps)
         elif logits_mode == "argmax":  # greedy: (idx, val) of this rank's vocab shard, argmax fused in the GEMM
             logits = ops.linear_argmax(hb.reshape(b, s, d)[:, -1].contiguous(), self.lm_head, rms_eps=self.eps)
         else:

@@ -36,7 +36,8 @@ class LLaMAAttention:
         return self.model.layers[self.layer_idx]
 
     def __call__(self, h, hb, positions, cache, slot0, kv_start, key_mask, seq_len: int,
-                 output_attentions: bool = False, pk: Optional["PackedActs"] = None) -> Optional[torch.Tensor]:
+                 output_attentions: bool = False, pk: Optional["PackedActs"] = None,
+                 few_query: bool = False) -> Optional[torch.Tensor]:
         m, lw = self.model, self.weights
         kc, vc = cache.layer(self.layer_idx)
         # the indirect beam cache: decode reads K / V through the cache's ancestry table (never on a row view: prefill)
@@ -82,7 +83,8 @@ class LLaMAAttention:
             a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask, beam_anc=anc, num_beams=nbeams)
         else:
             att_p = pk.att if pk is not None and ops.attention_packs(q4, kc, key_mask, anc) else None
-            a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask, out_packed=att_p, beam_anc=anc, num_beams=nbeams)
+            a = ops.attention(q4, kc, vc, slot0, kv_start, key_mask, out_packed=att_p, beam_anc=anc, num_beams=nbeams,
+                              few_query=few_query)
         m._row_parallel(a, lw.o, h, hb, x_packed=att_p, mirror_packed=pk.hb if pk else None)
         if pk is not None and pk.hb is not None:
             pk.hb_ok = True
@@ -110,8 +112,9 @@ class LLaMABlock:
         self.feed_forward = LLaMAMLP(model, layer_idx)
 
     def __call__(self, h, hb, positions, cache, slot0, kv_start, key_mask, seq_len: int,
-                 output_attentions: bool = False, pk: Optional["PackedActs"] = None):
-        w = self.attention(h, hb, positions, cache, slot0, kv_start, key_mask, seq_len, output_attentions, pk)
+                 output_attentions: bool = False, pk: Optional["PackedActs"] = None, few_query: bool = False):
+        w = self.attention(h, hb, positions, cache, slot0, kv_start, key_mask, seq_len, output_attentions, pk,
+                           few_query)
         self.feed_forward(h, hb, pk)
         return w
 
@@ -147,7 +150,7 @@ class LLaMABlockCollection:
         return len(self.blocks)
 
     def __call__(self, h, hb, positions, cache, slot0, kv_start, key_mask, seq_len: int,
-                 output_hidden_states: bool = False, output_attentions: bool = False):
+                 output_hidden_states: bool = False, output_attentions: bool = False, few_query: bool = False):
         hidden, attns = [], []
         b = hb.shape[0] // seq_len
         rows = hb.shape[0]
@@ -159,7 +162,7 @@ class LLaMABlockCollection:
         for blk in self.blocks:
             if output_hidden_states:
                 hidden.append(h.reshape(b, seq_len, -1).clone())
-            w = blk(h, hb, positions, cache, slot0, kv_start, key_mask, seq_len, output_attentions, pk)
+            w = blk(h, hb, positions, cache, slot0, kv_start, key_mask, seq_len, output_attentions, pk, few_query)
             if output_attentions:
                 attns.append(w)
         return hidden, attns

@@ -780,7 +780,7 @@ def attention_packs(q: torch.Tensor, k_cache: torch.Tensor, key_mask: Optional[t
 def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slot0, kv_start: torch.Tensor,
               key_mask: Optional[torch.Tensor] = None, max_kv: Optional[int] = None,
               out_packed: Optional[torch.Tensor] = None, beam_anc: Optional[torch.Tensor] = None,
-              num_beams: int = 0) -> torch.Tensor:
+              num_beams: int = 0, few_query: bool = False) -> torch.Tensor:
     """Causal/padded attention of ``q [B, S, H, Dh]`` (queries at cache slots slot0+s)
     against ``[B, Hkv, T, Dh]`` caches. Returns ``[B*S, H*Dh]`` bf16.
 
@@ -789,7 +789,12 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
 
     ``beam_anc`` (uint8 ``[B, T]``) with ``num_beams = K``: the indirect beam cache. Row ``r = b*K + j`` reads key
     slot t from physical row ``b*K + min(beam_anc[r, t], K - 1)`` (``ref.attention_anc``; on the GPU
-    csrc/kernels/attn_decode_anc.hip). Decode only (S = 1), bf16 caches, no packed copy: ``ValueError`` otherwise."""
+    csrc/kernels/attn_decode_anc.hip). Decode only (S = 1), bf16 caches, no packed copy: ``ValueError`` otherwise.
+
+    ``few_query``: a launch of a few queries per row (the verify step of speculative decoding) asks for the few-query
+    decode kernel (csrc/kernels/attn_verify.hip: ``2 <= S``, ``S * H / Hkv <= 32``, bf16 caches, ``Dh == 128``, no
+    key mask). A shape its plan declines (csrc/kernels/attn_plan.h attn_verify_plan) runs what it runs without the
+    flag; with the default ``False`` every call does."""
     bsz, s, h, dh = q.shape
     if beam_anc is not None:
         if s != 1 or is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
@@ -821,6 +826,19 @@ def attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, slo
         e.attn_decode_anc(q, k_cache, v_cache, beam_anc, int(num_beams), slot_t, kv_start, key_mask, out, t_cap, ws,
                           tickets)
         return out
+    if few_query and s > 1:
+        # a few queries per row: the few-query decode kernel where its plan (csrc/kernels/attn_plan.h attn_verify_plan)
+        # takes the shape; a declined one falls through to the launch it gets without the flag
+        fp8 = is_fp8_kv(k_cache) or is_fp8_kv(v_cache)
+        rc, _why, _tiles, nsplit, ws_floats, n_tickets = e.attn_verify_plan_check(
+            bsz, s, h, k_cache.shape[1], dh, t_cap, fp8, key_mask is not None, False)
+        if rc == 0:
+            ws = tickets = None
+            if nsplit > 1:
+                ws = workspace.get("attn_verify", ws_floats, torch.float32, q.device)
+                tickets = workspace.get_zeroed("attn_verify_tickets", n_tickets, torch.int32, q.device)
+            e.attn_verify(q, k_cache, v_cache, slot_t, kv_start, out, t_cap, ws, tickets)
+            return out
     if is_fp8_kv(k_cache) or is_fp8_kv(v_cache):
         _check_kv8_pair(k_cache, v_cache)
         if out_packed is not None:
@@ -1190,6 +1208,36 @@ def kv_beam_reorder(cache, beam_idx: torch.Tensor, k: int) -> None:
             ref.kv_beam_reorder(t, beam_idx, k, int(cache.index_t.item()))
         else:
             ext().kv_beam_reorder(t, beam_idx.reshape(-1), cache.index_t, int(k))
+
+
+def prompt_lookup(sequences: torch.Tensor, cur_len: torch.Tensor, hist_start: torch.Tensor, tokens: torch.Tensor,
+                  max_ngram: int) -> None:
+    """Columns ``1 .. k`` of ``tokens`` int32 ``[B, k + 1]`` <- every row's ``k`` prompt-lookup drafts from its history
+    ``sequences[b, hist_start[b] : cur_len[0]]`` (``ref.prompt_lookup``; csrc/kernels/spec.hip). Column 0 stays."""
+    if not _is_gpu(sequences):
+        tokens[:, 1:] = ref.prompt_lookup(sequences, int(cur_len.item()), hist_start, tokens.shape[1] - 1, max_ngram)
+    else:
+        ext().prompt_lookup(sequences, cur_len, hist_start, tokens, int(max_ngram))
+
+
+def spec_accept(tgt: torch.Tensor, finished: torch.Tensor, sequences: torch.Tensor, cur_len: torch.Tensor,
+                tokens: torch.Tensor, positions: torch.Tensor, slot: torch.Tensor, pad: int,
+                stop: torch.Tensor) -> None:
+    """The accept step of prompt-lookup decoding, in place on the decode state (``ref.spec_accept``;
+    csrc/kernels/spec.hip): the drafts ``tokens[:, 1:]`` against the verify step's greedy tokens ``tgt [B, k + 1]``;
+    the whole batch appends its shortest accepted run plus one token to ``sequences``, and ``cur_len``, ``slot``, every
+    column of ``positions [B, k + 1]`` and ``tokens[:, 0]`` (the last token written) move with it. ``stop``: int32 [8],
+    unused entries -1. B <= 64."""
+    if _is_gpu(tokens):
+        ext().spec_accept(tgt, finished, sequences, cur_len, tokens, positions, slot, int(pad), stop)
+        return
+    cl = int(cur_len.item())
+    n = ref.spec_accept(tokens[:, 1:], tgt, finished, sequences, cl, pad, stop.tolist())
+    if n > 0:
+        tokens[:, 0] = sequences[:, cl + n - 1]
+        positions.copy_(positions[:, :1] + n + torch.arange(positions.shape[1], dtype=positions.dtype))
+        cur_len.add_(n)
+        slot.add_(n)
 
 
 def beam_anc_update(anc: torch.Tensor, beam_idx: torch.Tensor, k: int, slot: torch.Tensor) -> None:

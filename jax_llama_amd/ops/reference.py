@@ -875,3 +875,58 @@ def process_logits(logits: torch.Tensor, sequences: torch.Tensor, cur_len: int, 
         if int(cur_len) < cfg.min_len:
             row[stops] = -math.inf
     return logits
+
+
+# ----------------------------------------------------------------------------------
+# Prompt-lookup speculative decoding (the README's "Prompt-lookup decoding" section; csrc/kernels/spec.hip)
+# ----------------------------------------------------------------------------------
+def prompt_lookup(sequences: torch.Tensor, cur_len: int, hist_start: torch.Tensor, k: int,
+                  max_ngram: int) -> torch.Tensor:
+    """The ``k`` draft tokens of every row, int32 ``[B, k]``: HF's ``PromptLookupCandidateGenerator`` rule with a fixed
+    draft count. Per row, for ``n = max_ngram .. 1``: the earliest ``p`` in ``[hist_start[b], cur_len - n)`` with
+    ``sequences[b, p : p + n] == sequences[b, cur_len - n : cur_len]`` (``p < cur_len - n``: a token follows the match);
+    the drafts are the ``k`` tokens from ``p + n`` on. A continuation that reaches ``cur_len`` first, and a row with no
+    match at any ``n``, fill with the row's last token ``sequences[b, cur_len - 1]``."""
+    b, length = sequences.shape
+    cl = max(1, min(int(cur_len), length))
+    out = torch.empty(b, k, dtype=torch.int32)
+    for r in range(b):
+        row = sequences[r].tolist()
+        hs = max(0, min(int(hist_start[r]), cl))
+        drafts = []
+        for n in range(int(max_ngram), 0, -1):
+            tail = row[cl - n:cl]
+            p = next((p for p in range(hs, cl - n) if row[p:p + n] == tail), None)
+            if p is not None:
+                drafts = row[p + n:min(p + n + k, cl)]
+                break
+        out[r] = torch.tensor(drafts + [row[cl - 1]] * (k - len(drafts)), dtype=torch.int32)
+    return out.to(sequences.device)
+
+
+def spec_accept(drafts: torch.Tensor, tgt: torch.Tensor, finished: torch.Tensor, sequences: torch.Tensor,
+                cur_len: int, pad: int, stop_ids) -> int:
+    """One accept step, in place on ``finished [B]`` and ``sequences [B, L]``; returns ``n``, the tokens the whole batch
+    advances by. ``tgt[r, s]`` is the greedy token after input ``s`` of the verify step ``[last, drafts[r]]``; row ``r``
+    accepts ``a_r`` = its leading ``j`` with ``drafts[r, j] == tgt[r, j]``; ``n = 1 + min a_r`` over the unfinished rows
+    (``k`` when none is left), clamped to ``[0, L - cur_len]``. Every row appends ``tgt[r, :n]`` at ``cur_len`` with
+    the decode loop's semantics per token: a finished row writes ``pad``, a stop id finishes the row."""
+    b, k = drafts.shape
+    length = sequences.shape[1]
+    stops = {int(t) for t in stop_ids if int(t) >= 0}
+    a_min = k
+    for r in range(b):
+        if not int(finished[r]):
+            a = 0
+            while a < k and int(drafts[r, a]) == int(tgt[r, a]):
+                a += 1
+            a_min = min(a_min, a)
+    n = max(0, min(1 + a_min, length - int(cur_len)))
+    for r in range(b):
+        fin = bool(int(finished[r]))
+        for i in range(n):
+            t = int(pad) if fin else int(tgt[r, i])
+            fin = fin or t in stops
+            sequences[r, int(cur_len) + i] = t
+        finished[r] = int(fin)
+    return n

@@ -75,6 +75,43 @@ def decode_latency(model, batch: int, prompt_len: int = 128, gen_len: int = 256,
             "kernels_per_layer": round(kernels / model.config.num_hidden_layers, 2) if kernels >= 0 else None}
 
 
+def lookup_latency(model, batch: int, prompt_len: int = 128, steps: int = 32, num_drafts: int = 3, max_ngram: int = 2,
+                   period: int = 0, seed: int = 0) -> Dict[str, float]:
+    """Prompt-lookup decoding (``LookupEngine``): ``steps`` graph replays of the verify step after a prefill, in a cache
+    long enough that no step is clamped (``prompt_len + steps * (num_drafts + 1) + 1``). ``verify_ms_per_step`` is the
+    time of one step whatever it accepts; ``tokens_per_step`` the tokens the batch advanced by per step on THIS prompt
+    (``period`` > 0: the synthetic prompt repeats its first ``period`` tokens, text a lookup can match; 0: random
+    tokens), and ``decode_ms_per_token`` their quotient."""
+    from .engine import LookupEngine
+    max_len = prompt_len + steps * (num_drafts + 1) + 1
+    eng = LookupEngine(model, batch, max_len, num_drafts, max_ngram, use_graph=True)
+    eng.gc = GenerationConfig(max_length=max_len, do_sample=False, pad_token_id=0, eos_token_id=-1,
+                              prompt_lookup_num_tokens=num_drafts, max_matching_ngram_size=max_ngram)
+    prompts = synthetic_prompts(model.config.vocab_size, batch, prompt_len, seed)
+    if period > 0:
+        prompts = prompts[:, :period].repeat(1, (prompt_len + period - 1) // period)[:, :prompt_len].contiguous()
+    dev = model.device
+    eng.prefill(prompts, None)  # cold: autotunes, grows the workspaces
+    eng._decode_step()
+    eng._ensure_graph()
+    eng._graph.replay()
+    eng.prefill(prompts, None)
+    torch.cuda.synchronize(dev)
+    start = int(eng.cur_len.item())
+    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    ev0.record()
+    for _ in range(steps):
+        eng._graph.replay()
+    ev1.record()
+    torch.cuda.synchronize(dev)
+    ms = ev0.elapsed_time(ev1) / steps
+    tps = (int(eng.cur_len.item()) - start) / steps
+    del eng
+    return {"batch": batch, "prompt_lookup": num_drafts, "max_ngram": max_ngram, "prompt_period": period,
+            "steps": steps, "verify_ms_per_step": round(ms, 4), "tokens_per_step": round(tps, 3),
+            "decode_ms_per_token": round(ms / tps, 4)}
+
+
 def graph_kernels(graph) -> int:
     """Kernel nodes of a captured torch.cuda.CUDAGraph (hipGraphGetNodes; -1 when the raw graph is unavailable)."""
     from .. import ops

@@ -69,6 +69,9 @@ class GenerationConfig:
     length_penalty: float = 1.0
     early_stopping: object = False  # False, True or "never"
     num_return_sequences: int = 1
+    # prompt-lookup speculative decoding (the README's "Prompt-lookup decoding" section; LookupEngine): HF's names
+    prompt_lookup_num_tokens: Optional[int] = None  # k drafts per step from the row's own history (None: off)
+    max_matching_ngram_size: int = 2
 
 
 # prompt tokens per prefill forward (DecodeEngine._prefill_rows): larger batches run their prefill in row chunks
@@ -256,6 +259,8 @@ def _sample(model, logits_local: torch.Tensor, gc: GenerationConfig, gen: Option
 class DecodeEngine:
     """Owns the KV cache and the device-resident decode state for one (B, max_length)."""
 
+    extra_slots = 0  # cache slots past max_length (LookupEngine: its rejected drafts are written there)
+
     def __init__(self, model, batch_size: int, max_length: int, use_graph: Optional[bool] = None,
                  check_every: int = 16):
         self.model = model
@@ -267,7 +272,7 @@ class DecodeEngine:
             use_graph = dev.type == "cuda" and os.environ.get("JLA_NO_GRAPH", "0") != "1"
         self.use_graph = use_graph
         self.check_every = check_every
-        self.cache = model.init_cache(batch_size, max_length)
+        self.cache = model.init_cache(batch_size, max_length + self.extra_slots)
         i32 = dict(dtype=torch.int32, device=dev)
         self.tokens = torch.zeros(batch_size, 1, **i32)
         self.positions = torch.zeros(batch_size, 1, **i32)
@@ -351,7 +356,7 @@ class DecodeEngine:
         else:
             mask = attention_mask.to("cpu", torch.int32)
         positions = (mask.cumsum(-1) - 1).to(torch.int32)
-        ext_mask = torch.ones(b, self.max_length, dtype=torch.int32)
+        ext_mask = torch.ones(b, self.cache.max_length, dtype=torch.int32)
         ext_mask[:, :s] = mask
         from ..models.llama import mask_to_kv_start
         kv_start, key_mask = mask_to_kv_start(ext_mask, dev)
@@ -521,6 +526,7 @@ class DecodeEngine:
             if step % self.check_every == 0 and self._poll():
                 break
         self._check()
+        self.steps = step
         return self.sequences
 
 
@@ -680,6 +686,91 @@ class BeamEngine(DecodeEngine):
         return seqs[:, :n].reshape(-1, self.max_length).clone(), scores[:, :n].reshape(-1).clone()
 
 
+class LookupEngine(DecodeEngine):
+    """Greedy decoding with prompt-lookup speculation (``prompt_lookup_num_tokens = k``): each step emits between 1 and
+    ``k + 1`` tokens for one stream of the weights. A step is
+
+      ``ops.prompt_lookup``   k draft tokens per row from an n-gram match in the row's own history (no draft model);
+      ``forward_tokens``      on ``[last token, drafts]``, ``S = k + 1`` positions per row, attention by the few-query
+                              decode kernel (``few_query=True``), the greedy token after every position;
+      ``ops.spec_accept``     row r accepts its leading drafts that equal those tokens; the WHOLE batch advances by
+                              ``1 + min_r a_r`` (unfinished rows), so the one device slot counter stays.
+
+    Every launch reads its inputs from device state, so the step is captured once and replayed like the plain one. The
+    cache rows a step writes past the accepted prefix are overwritten by the next step; the cache holds ``k`` slots
+    past ``max_length`` so that no such write is clamped. A step that finds the buffer full changes nothing."""
+
+    def __init__(self, model, batch_size: int, max_length: int, num_drafts: int, max_ngram: int = 2,
+                 use_graph: Optional[bool] = None, check_every: int = 4):
+        if model.comm.size > 1:
+            raise NotImplementedError("prompt-lookup decoding under tensor parallelism is not supported")
+        self.k = int(num_drafts)
+        self.max_ngram = int(max_ngram)
+        self.extra_slots = self.k
+        super().__init__(model, batch_size, max_length, use_graph, check_every)
+        i32 = dict(dtype=torch.int32, device=self.device)
+        self.tokens = torch.zeros(batch_size, self.k + 1, **i32)
+        self.positions = torch.zeros(batch_size, self.k + 1, **i32)
+        self._first = (torch.zeros(batch_size, 1, **i32), torch.zeros(batch_size, 1, **i32))
+        self.steps = 0  # verify steps the last run launched (tools: tokens per step; exact with check_every = 1)
+
+    def prefill(self, input_ids, attention_mask):
+        # the plain prefill and first token on one-column state buffers, then column 0 and every column's position
+        tokens, positions = self.tokens, self.positions
+        self.tokens, self.positions = self._first
+        try:
+            cur = super().prefill(input_ids, attention_mask)
+        finally:
+            self.tokens, self.positions = tokens, positions
+        tokens[:, :1] = self._first[0]
+        positions.copy_(self._first[1] + torch.arange(self.k + 1, dtype=torch.int32, device=self.device))
+        return cur
+
+    def _set_processors(self, mask, s):
+        # the history starts and the stop set always: prompt_lookup and spec_accept read them
+        super()._set_processors(mask, s)
+        first = torch.where(mask.bool().any(1), mask.ne(0).to(torch.int32).argmax(1), torch.full((mask.shape[0],), s))
+        self.hist_start.copy_(first.to(torch.int32))
+        self.stop_ids.copy_(ops.id_buffer(stop_ids(self.gc), ops.PROC_MAX_STOP, "cpu"))
+
+    def _decode_step(self):
+        ops.prompt_lookup(self.sequences, self.cur_len, self.hist_start, self.tokens, self.max_ngram)
+        pair, *_ = self.model.forward_tokens(self.tokens, self.positions, self.cache, self.cache.index_t,
+                                             self.kv_start, self.key_mask, logits_mode="argmax_all", few_query=True)
+        tgt = _greedy(self.model, pair).reshape(self.b, self.k + 1)
+        ops.spec_accept(tgt, self.finished, self.sequences, self.cur_len, self.tokens, self.positions,
+                        self.cache.index_t, int(self.gc.pad_token_id), self.stop_ids)
+
+    def _graph_state(self):
+        return super()._graph_state() + (self.k, self.max_ngram, self.cache.kv_format)
+
+    def _poll(self) -> bool:
+        done = bool(self.finished.all().item()) or int(self.cur_len.item()) >= self.max_length
+        self._check()
+        return done
+
+def validate_lookup(gc: GenerationConfig, model, batch_size: int) -> None:
+    """ValueError / NotImplementedError for ``prompt_lookup_num_tokens`` settings the lookup loop does not serve."""
+    k, n = gc.prompt_lookup_num_tokens, gc.max_matching_ngram_size
+    rep = model.n_heads // model.n_kv_heads
+    if isinstance(k, bool) or not isinstance(k, int) or k < 1:
+        raise ValueError(f"prompt_lookup_num_tokens must be an int >= 1, got {k!r}")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"max_matching_ngram_size must be an int >= 1, got {n!r}")
+    if (k + 1) * rep > 32:
+        raise ValueError(f"prompt_lookup_num_tokens: (k + 1) x {rep} query heads per kv head must be <= 32, got k = {k}")
+    if batch_size > 64:
+        raise ValueError(f"prompt-lookup decoding serves batches of at most 64 rows, got {batch_size}")
+    if gc.do_sample:
+        raise ValueError("prompt-lookup decoding is greedy: prompt_lookup_num_tokens needs do_sample=False")
+    if gc.num_beams != 1:
+        raise ValueError("prompt-lookup decoding does not combine with beam search (num_beams > 1)")
+    if processors_active(gc) or truncation_active(gc):
+        raise ValueError("prompt-lookup decoding takes no logits processors and no min_p / typical_p")
+    if model.comm.size > 1:
+        raise NotImplementedError("prompt-lookup decoding under tensor parallelism is not supported")
+
+
 def _anc_reorder(cache, beam_idx, k):
     """The indirect beam cache's ``reorder`` hook: the rows stay, the ancestry table takes the permutation."""
     ops.beam_anc_update(cache.beam_anc, beam_idx, k, cache.index_t)
@@ -707,17 +798,21 @@ def drop_engines(model) -> int:
     return len(keys)
 
 
-def get_engine(model, batch_size: int, max_length: int, num_beams: int = 1) -> DecodeEngine:
-    """Per-(model, B, max_length, num_beams) engines (each owns a KV cache and a captured decode graph), kept in
+def get_engine(model, batch_size: int, max_length: int, num_beams: int = 1, lookup=None) -> DecodeEngine:
+    """Per-(model, B, max_length, num_beams, lookup) engines (each owns a KV cache and a captured decode graph), kept in
     LRU order and bounded by the bytes of their KV caches. The model's KV-cache format is part of the key: an engine
-    owns a cache of one format. ``num_beams > 1``: a BeamEngine over ``B * num_beams`` cache rows."""
+    owns a cache of one format. ``num_beams > 1``: a BeamEngine over ``B * num_beams`` cache rows. ``lookup = (k,
+    max_ngram)``: a LookupEngine."""
     fmt = getattr(model, "kv_cache_format", "bf16")
     key = (id(model), batch_size, max_length, fmt, num_beams, getattr(model, "beam_cache", "reorder"))
+    if lookup is not None:
+        key += (tuple(lookup),)
     eng = _ENGINES.get(key)
     if eng is not None:
         _ENGINES.move_to_end(key)
         return eng
-    need = (model.config.num_hidden_layers * 2 * batch_size * num_beams * model.n_kv_heads * max_length *
+    slots = max_length + (lookup[0] if lookup is not None else 0)
+    need = (model.config.num_hidden_layers * 2 * batch_size * num_beams * model.n_kv_heads * slots *
             kv_row_bytes(fmt, model.head_dim))
     budget = _engine_budget(model)
     held = sum(e.cache.nbytes() for e in _ENGINES.values())
@@ -725,8 +820,11 @@ def get_engine(model, batch_size: int, max_length: int, num_beams: int = 1) -> D
         _, old = _ENGINES.popitem(last=False)
         held -= old.cache.nbytes()
         del old
-    eng = (DecodeEngine(model, batch_size, max_length) if num_beams == 1
-           else BeamEngine(model, batch_size, num_beams, max_length))
+    if lookup is not None:
+        eng = LookupEngine(model, batch_size, max_length, lookup[0], lookup[1])
+    else:
+        eng = (DecodeEngine(model, batch_size, max_length) if num_beams == 1
+               else BeamEngine(model, batch_size, num_beams, max_length))
     _ENGINES[key] = eng
     return eng
 
@@ -760,6 +858,10 @@ def generate(model, input_ids, attention_mask=None, generation_config: Optional[
     if isinstance(gc.eos_token_id, (list, tuple)):
         gc.eos_token_id = list(gc.eos_token_id)
     validate_processors(gc, model.config.vocab_size)
+    lookup = None
+    if gc.prompt_lookup_num_tokens is not None:
+        validate_lookup(gc, model, b)
+        lookup = (gc.prompt_lookup_num_tokens, gc.max_matching_ngram_size)
     if prng_key is not None:
         gc.seed = int(prng_key) if not torch.is_tensor(prng_key) else int(prng_key.reshape(-1)[0])
     if s >= gc.max_length:
@@ -769,7 +871,7 @@ def generate(model, input_ids, attention_mask=None, generation_config: Optional[
             return GenerateOutput(sequences=out.repeat_interleave(n, 0),
                                   scores=torch.zeros(b * n, dtype=torch.float32, device=model.device))
         return GenerateOutput(sequences=out)
-    eng = get_engine(model, b, gc.max_length, gc.num_beams)
+    eng = get_engine(model, b, gc.max_length, gc.num_beams, lookup)
     res = eng.run(ids, attention_mask if attention_mask is None or torch.is_tensor(attention_mask)
                   else torch.as_tensor(attention_mask), gc)
     if beams:

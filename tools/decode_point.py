@@ -48,13 +48,17 @@ def main():
                     "processors off and on, alternately (record field `processors`)")
     ap.add_argument("--min-p", type=float, default=0.0, help="with --sample: every point with min_p off and on, "
                     "alternately (record field `min_p`; on, every top_k runs the full-vocabulary sampler)")
+    ap.add_argument("--prompt-lookup", type=int, default=0, metavar="K",
+                    help="K > 0: after every plain point, the same model with prompt-lookup decoding "
+                    "(prompt_lookup_num_tokens = K; runtime/benchmark.py lookup_latency) on a prompt that repeats a "
+                    "16-token period and on a random one: ms per verify step, tokens per step, ms per token")
     ap.add_argument("--tune-report", action="store_true", help="print the decode-kernel choices and the graph-timed "
                     "microseconds of every candidate measured (ops/autotune.py)")
     args = ap.parse_args()
     import torch
     from jax_llama_amd.config import get_preset
     from jax_llama_amd.models import LLaMAForCausalLM
-    from jax_llama_amd.runtime.benchmark import decode_latency
+    from jax_llama_amd.runtime.benchmark import decode_latency, lookup_latency
     cfg = get_preset(args.model, max_seq_len=2048)
     comm = None
     if args.tp_proxy > 1:
@@ -100,6 +104,13 @@ def main():
                 r["hbm_roofline_ms"] = round(m.streamed_weight_bytes_per_token() / 6.29e12 * 1e3, 4)
                 print(json.dumps(r), flush=True)
                 torch.cuda.empty_cache()
+                if args.prompt_lookup > 0 and not args.sample and proc is None and args.tp_proxy == 1:
+                    for period in (16, 0):
+                        lr = lookup_latency(m, b, args.prompt_len, min(args.steps, 32), args.prompt_lookup,
+                                            period=period)
+                        lr.update(model=args.model, weights=wf, kv=kv, rep=rep, plain_ms_per_token=r["decode_ms_per_token"])
+                        print(json.dumps(lr), flush=True)
+                        torch.cuda.empty_cache()
     if args.tune_report:
         from jax_llama_amd.ops import autotune
         for (m, n, k, _), t in autotune.measured().items():
